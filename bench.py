@@ -13,7 +13,24 @@ packed moments (and a scalar one for the θ3 trace slices).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
                     [--scaling strong|weak] [--dist-backend nccl|gloo]
-                    [--no-cpu] [--no-vae] [--no-cv] [--no-weak]
+                    [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-vae] [--no-cv] [--no-prep] [--no-weak]]
+
+A plain run does what the headline figure needs and no more: it generates the
+spectra, runs W warm-up steps and K timed steps, writes the last step's
+results if ``--dump-outputs DIR`` is given, and prints the result line.
+``--full`` adds every other measurement to that line: the per-phase breakdown
+(``phases_ms``, extra untimed steps), the weak-scaling run, the preprocessing
+line, the CV line, the CPU baseline and the VAE line; the ``--no-*`` switches
+and ``--phase-steps`` trim a full run.
+
+``--dump-outputs DIR`` writes what a caller of the timed path holds after the
+last timed step as ``DIR/<name>.npy`` (float32 / float64): ``pred`` (predict's
+return value), the fit-set ``T``, ``T2``, ``Q``, the loadings ``P``, ``xmean``,
+``evals`` and ``limits`` (T2, Q, D).  An array above 8 MiB is cut to a fixed,
+seeded sample of its rows, listed in ``<name>_rows.npy``.  The spectra depend
+on the arguments alone, so two builds run with the same arguments can be
+compared array for array.  At N > 1 rank 0 writes its row block's arrays.
 
 Multi-GPU: ``--gpus N`` with N > 1 and no ``WORLD_SIZE`` in the environment
 starts N rank processes itself (a ``torch.distributed.run`` child; this
@@ -21,16 +38,16 @@ parent never touches the GPU) and exits with its status; launched under
 torch.distributed.run (the driver's form) it runs as one rank.  Scaling is
 STRONG by default: R = 1M rows in total, split into contiguous row blocks
 (the global matrix does not depend on N: ocm/synth.py), value = R / the
-max-over-ranks step time.  At N > 1 the line also carries the weak-scaling
-run (R rows per GPU) under ``weak``.  ``cv`` is C3: class-wise 10-fold CV
-(the fold engine, ocm/cv.py) of 1M×2048 spectra (10 % other class) sharded
-the same way.  ``phases_ms`` is each rank's per-phase time (HIP events on
-the launch stream) from extra, untimed steps.
+max-over-ranks step time.  With ``--full``: at N > 1 the line also carries
+the weak-scaling run (R rows per GPU) under ``weak``; ``cv`` is C3: class-wise
+10-fold CV (the fold engine, ocm/cv.py) of 1M×2048 spectra (10 % other class)
+sharded the same way; ``phases_ms`` is each rank's per-phase time (HIP events
+on the launch stream) from extra, untimed steps.
 
 Prints ONE JSON line (rank 0).  The `roofline` object is for the dominant
 kernel, k_gram8e: algorithmic FLOP per launch = this rank's rows × p(p+1)
 (symmetric Gram) ÷ its mean duration, timed live with HIP events around every
-launch in the timed region.  `cpu_baseline` times the oracle's
+launch in the timed region.  `cpu_baseline` (``--full``) times the oracle's
 reference-precision path (float32 full SVD + randomized PCA(k) + NumPy
 scoring) on a bounded row sample on this host (N = 1 only).
 """
@@ -71,6 +88,11 @@ def parse(argv=None):
     ap.add_argument("--p", type=int, default=2048)
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--cpu-sample", type=int, default=131072, help="rows for the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (phase breakdown, weak scaling, preprocessing, CV, "
+                         "CPU baseline, VAE); the --no-* switches below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-vae", action="store_true", help="skip the secondary VAE train-steps/s measurement")
     ap.add_argument("--vae-steps", type=int, default=200)
@@ -78,7 +100,8 @@ def parse(argv=None):
     ap.add_argument("--no-prep", action="store_true", help="skip the preprocessing + fit + score extra line")
     ap.add_argument("--cv-reps", type=int, default=3)
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the weak-scaling extra run")
-    ap.add_argument("--phase-steps", type=int, default=3, help="untimed steps with per-phase events (0 = off)")
+    ap.add_argument("--phase-steps", type=int, default=3,
+                    help="--full: untimed steps with per-phase events (0 = off)")
     ap.add_argument("--gram-mode", default=GRAM_MODE_DEFAULT, choices=["f32", "bf16x3", "i8x3", "i8x3k32"],
                     help="Gram kernel: int8 digit split (default), bf16x3 split or FP32 MFMA")
     return ap.parse_args(argv)
@@ -307,8 +330,43 @@ def _timed(rk, step, steps, warmup):
     return rk.max(time.perf_counter() - t0)
 
 
-def run_simca(args, rk, n_total):
-    """The SIMCA fit + score step on this rank's rows of an n_total-row matrix."""
+DUMP_ARRAY_BYTES = 8 << 20  # per array; the per-row arrays, their row lists and the small ones stay under 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, result):
+    """Write the last timed step's results (``--dump-outputs``): what the
+    caller of fit + predict holds.  Arrays go out as float32 / float64; one
+    above DUMP_ARRAY_BYTES is cut to a seeded, sorted sample of its rows
+    (the same rows on every run of the same shape), listed in <name>_rows."""
+    import numpy as np
+    import torch
+
+    fit = result["fit"]
+    arrays = {"pred": result["pred"], "T": fit.T, "T2": fit.T2, "Q": fit.Q, "P": fit.P64, "xmean": fit.mean64,
+              "evals": fit.evals,
+              "limits": np.array([result["T2_limit"], result["Q_limit"], result["D_limit"]], dtype=np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if isinstance(a, torch.Tensor):
+            if a.dtype not in (torch.float32, torch.float64):
+                a = a.to(torch.float64)
+            row_bytes = max(1, a[0].numel() * a.element_size()) if a.dim() and a.shape[0] else 1
+            if a.dim() and a.shape[0] * row_bytes > DUMP_ARRAY_BYTES:
+                keep = DUMP_ARRAY_BYTES // row_bytes
+                rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=keep, replace=False))
+                a = a[torch.from_numpy(rows).to(a.device)]
+                np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def run_simca(args, rk, n_total, phase_steps=0, dump=None):
+    """The SIMCA fit + score step on this rank's rows of an n_total-row matrix;
+    ``phase_steps`` extra untimed steps give the per-phase breakdown, ``dump``
+    is the folder for the last timed step's results."""
     import torch
 
     from ocm import _lib, engine
@@ -332,11 +390,12 @@ def run_simca(args, rk, n_total):
             model.fit(X, y)
             result["pred"] = model.predict(X)
             info = model._model[0]
-            result.update(fit=model._fits[0], T2_limit=info["T2_limit"], Q_limit=info["Q_limit"])
+            result.update(fit=model._fits[0], T2_limit=info["T2_limit"], Q_limit=info["Q_limit"],
+                          D_limit=info["D_limit"])
         else:
             model = ShardedSIMCA(n_components=k, type="alt", t2lim="Fdist", qlim="jm").fit(X)
             result["pred"] = model.predict(X, out=pred)
-            result.update(fit=model.fit_, T2_limit=model.T2_limit, Q_limit=model.Q_limit)
+            result.update(fit=model.fit_, T2_limit=model.T2_limit, Q_limit=model.Q_limit, D_limit=model.D_limit)
 
     for _ in range(args.warmup):
         step()
@@ -347,16 +406,18 @@ def run_simca(args, rk, n_total):
     dt = _timed(rk, step, args.steps, 0)
     ctx.set_timing(False)
     timing = {name: ctx.read_timing(kid) for kid, name in enumerate(("gram", "score", "quant"))}
+    if dump is not None and rk.rank == 0:
+        dump_outputs(dump, result)
 
     phases = None
-    if args.phase_steps > 0:
+    if phase_steps > 0:
         timer = PhaseTimer(rk.device)
         engine.set_phase_timer(timer)
         try:
-            for _ in range(args.phase_steps):
+            for _ in range(phase_steps):
                 step()
                 timer.mark("predict_score")
-            phases = timer.summary(args.phase_steps)
+            phases = timer.summary(phase_steps)
         finally:
             engine.set_phase_timer(None)
     accepted = float(result["pred"].sum().item())
@@ -476,7 +537,8 @@ def main():
     engine.set_gram_mode(args.gram_mode)
     p, k = args.p, args.k
     n_total = args.rows if args.scaling == "strong" else args.rows * rk.world
-    head = run_simca(args, rk, n_total)
+    full = args.full
+    head = run_simca(args, rk, n_total, phase_steps=args.phase_steps if full else 0, dump=args.dump_outputs)
     n = head["n_local"]
     dt = head["seconds"]
     ms_per_step = dt / args.steps * 1e3
@@ -570,27 +632,27 @@ def main():
     phases = rk.gather(head["phases"])
     if head["phases"] is not None and rk.rank == 0:
         out["phases_ms"] = {f"rank{r}": ph for r, ph in enumerate(phases)}
-    if rk.world > 1 and args.scaling == "strong" and not args.no_weak:
-        weak = run_simca(args, rk, args.rows * rk.world)
+    if full and rk.world > 1 and args.scaling == "strong" and not args.no_weak:
+        weak = run_simca(args, rk, args.rows * rk.world, phase_steps=args.phase_steps)
         out["weak"] = {"scaling": "weak", "rows_per_gpu": weak["n_local"], "rows_total": args.rows * rk.world,
                        "value": round(args.rows * rk.world * args.steps / weak["seconds"], 1), "unit": "spectra/s",
                        "ms_per_step": round(weak["seconds"] / args.steps * 1e3, 3)}
-    if rk.world == 1 and not args.no_prep:
+    if full and rk.world == 1 and not args.no_prep:
         try:
             out["prep_fit_score"] = run_prep(args, rk, args.rows)
         except Exception as e:  # report, never fail the primary number
             out["prep_fit_score"] = {"error": repr(e)}
-    if not args.no_cv:
+    if full and not args.no_cv:
         try:
             out["cv"] = run_cv(args, rk, args.rows if args.scaling == "strong" else args.rows * rk.world)
         except Exception as e:  # report, never fail the primary number
             out["cv"] = {"error": repr(e)}
-    if rk.rank == 0 and rk.world == 1 and not args.no_cpu:
+    if full and rk.rank == 0 and rk.world == 1 and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, p, k)
         except Exception as e:  # report, never fail the GPU number
             out["cpu_baseline"] = {"error": repr(e)}
-    if rk.world == 1 and not args.no_vae:
+    if full and rk.world == 1 and not args.no_vae:
         try:
             out["vae"] = vae_bench(rk.device, args.vae_steps, 10)
         except Exception as e:  # report, never fail the primary number

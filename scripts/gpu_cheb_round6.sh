@@ -15,5 +15,5 @@ for S in bench nuts geom; do
 done
 unset OCM_LIB OCM_ALLOW_EXP_LIB
 cat $OUT/eig_ab.jsonl
-timeout -k 10 300 python -u bench.py --rows 125000 --steps 20 --warmup 3 --no-cpu --no-vae --no-cv --no-prep > $OUT/share.log 2>&1 && tail -1 $OUT/share.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"
-timeout -k 10 400 python -u bench.py --steps 5 --warmup 2 --no-cpu --no-vae --no-cv > $OUT/bench_prep.log 2>&1 && tail -1 $OUT/bench_prep.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], json.dumps(d.get('prep_fit_score')))"
+timeout -k 10 300 python -u bench.py --full --rows 125000 --steps 20 --warmup 3 --no-cpu --no-vae --no-cv --no-prep > $OUT/share.log 2>&1 && tail -1 $OUT/share.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"
+timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 2 --no-cpu --no-vae --no-cv > $OUT/bench_prep.log 2>&1 && tail -1 $OUT/bench_prep.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], json.dumps(d.get('prep_fit_score')))"

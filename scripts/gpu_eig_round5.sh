@@ -9,4 +9,4 @@ timeout -k 10 120 python scripts/bench_eig.py --reps 20 > $OUT/eig.log 2>&1 && c
 timeout -k 10 200 rocprofv3 --kernel-trace -d $OUT/prof -o run --output-format csv -- python3 bench.py --rows 125000 --steps 3 --warmup 1 --no-cpu --no-vae --no-cv --no-prep --phase-steps 0 > $OUT/trace_bench.log 2>&1 && tail -1 $OUT/trace_bench.log | cut -c1-300
 python scripts/trace_timeline.py $OUT/prof/run_kernel_trace.csv k_randn > $OUT/timeline.txt 2>&1; tail -60 $OUT/timeline.txt
 rm -f $OUT/prof/*_kernel_trace.csv
-timeout -k 10 200 python bench.py --rows 125000 --steps 20 --no-cpu --no-vae --no-cv --no-prep > $OUT/share.log 2>&1 && tail -1 $OUT/share.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"
+timeout -k 10 200 python bench.py --full --rows 125000 --steps 20 --no-cpu --no-vae --no-cv --no-prep > $OUT/share.log 2>&1 && tail -1 $OUT/share.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"

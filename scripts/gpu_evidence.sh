@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT="gpurun_out/${TAG:-evidence}"
 mkdir -p "$OUT"
 echo "== share125k ($(date +%T))"
-timeout -k 10 300 python -u bench.py --rows 125000 --steps 20 --warmup 3 --phase-steps 5 --no-cpu --no-vae --no-cv \
+timeout -k 10 300 python -u bench.py --full --rows 125000 --steps 20 --warmup 3 --phase-steps 5 --no-cpu --no-vae --no-cv \
   > "$OUT/share125k.log" 2>&1
 tail -n 1 "$OUT/share125k.log"
 echo "== vae trace ($(date +%T))"

@@ -21,11 +21,11 @@ if [ "${PMC:-1}" = 1 ]; then
 fi
 if [ "${BENCH:-1}" = 1 ]; then
   echo "== bench ($(date +%T))"
-  timeout -k 10 600 python -u bench.py > "$OUT/bench.log" 2>&1
+  timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1
   tail -n 1 "$OUT/bench.log" | head -c 1500; echo
   echo "== prof ($(date +%T))"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-    -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-vae > "$OUT/prof.log" 2>&1
+    -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-vae > "$OUT/prof.log" 2>&1
   rm -f "$OUT"/prof/*/*_kernel_trace.csv "$OUT"/prof/*_kernel_trace.csv
 fi
 echo "done"

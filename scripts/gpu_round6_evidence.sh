@@ -24,10 +24,10 @@ if [ "${TESTS:-1}" = 1 ]; then
   step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  step bench 500 python3 -u bench.py
-  step share125k 300 python3 -u bench.py --rows 125000 --no-cpu --no-vae --no-cv --no-prep --steps 20
-  step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 -u bench.py --no-cpu --no-vae --no-cv --no-prep --steps 5
-  python3 scripts/trace_by_grid.py "$O/prof/run_kernel_trace.csv" "$O/headline_by_grid.md" "headline workload (bench.py --no-cpu --no-vae --no-cv --no-prep --steps 5): kernel trace by launch shape" || exit 6
+  step bench 500 python3 -u bench.py --full
+  step share125k 300 python3 -u bench.py --full --rows 125000 --no-cpu --no-vae --no-cv --no-prep --steps 20
+  step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 -u bench.py --full --no-cpu --no-vae --no-cv --no-prep --steps 5
+  python3 scripts/trace_by_grid.py "$O/prof/run_kernel_trace.csv" "$O/headline_by_grid.md" "headline workload (bench.py --full --no-cpu --no-vae --no-cv --no-prep --steps 5): kernel trace by launch shape" || exit 6
   rm -f "$O/prof/run_kernel_trace.csv"
 fi
 if [ "${PMC:-1}" = 1 ]; then

@@ -31,10 +31,10 @@ if [ "${SMOKE:-0}" = 1 ]; then
   run smoke 300 "0" python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  run bench 600 "0" python -u bench.py ${BENCH_ARGS:-}
+  run bench 600 "0" python -u bench.py --full ${BENCH_ARGS:-}
 fi
 if [ "${PROF:-0}" = 1 ]; then
-  run prof 600 "0" rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-vae
+  run prof 600 "0" rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-vae
   rm -f "$OUT"/prof/*_kernel_trace.csv  # large; the stats file is the record
 fi
 if [ -n "${EXTRA:-}" ]; then
