@@ -443,6 +443,32 @@ int ocm_decide_f64(ocm_ctx* ctx, const double* T2, const double* Q, int64_t m, c
                    double* t2red_out, double* qred_out, double* dred_out, double* accept_out, int64_t accept_stride,
                    void* stream);
 
+/* ---- contribution plots (which variables put a sample outside the class) ----
+ * For every processed row (all rows, or X[rows[r]]), with y = x − μ, t = P·y
+ * and a = diag(1/λ) (the model of ocm_score_f32_diag, utils/SIMCA.py:67-71):
+ *   e_j = y_j − Σ_c t_c·P_cj          the residual;        Σ_j e_j² = Q
+ *   c_j = y_j · Σ_c (t_c·a_c)·P_cj    the T² contribution; Σ_j c_j  = T² (c_j may be negative)
+ * group [dev, nullable] m bytes: the profile group of each processed row, in
+ *   [0, ngroups), ngroups 1..4 (NULL: every row in group 0; rows with a larger
+ *   id contribute to no profile).
+ * E_out, C_out [dev, nullable] m×p (lde, ldc ≥ p): e and c.
+ * T2_out, Q_out [dev, nullable] m: the row sums Σ_j c_j and Σ_j e_j².
+ * prof_out [dev, nullable] ngroups×2×p: Σ_rows e_j² then Σ_rows c_j per group,
+ *   summed in a fixed order (two launches on one input give the same bits).
+ * Any p ≥ 1, 1 ≤ k ≤ min(p, 64), m ≥ 1, no alignment requirement.  With E_out
+ * and C_out NULL a launch writes O(m + p) values and its workspace does not
+ * grow with m.  f32: f32 MFMA products, t in f32 over ≤ 64 columns per chain
+ * flushed to f64, the residual formed in f32 (as the reference forms
+ * X − (T·P + μ) in float32); f64: fp64 MFMA throughout. */
+int ocm_contrib_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                    const double* P, const double* mu, const double* a_diag, int32_t k, const uint8_t* group,
+                    int32_t ngroups, float* E_out, int64_t lde, float* C_out, int64_t ldc, double* T2_out,
+                    float* Q_out, double* prof_out, void* stream);
+int ocm_contrib_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                    const double* P, const double* mu, const double* a_diag, int32_t k, const uint8_t* group,
+                    int32_t ngroups, double* E_out, int64_t lde, double* C_out, int64_t ldc, double* T2_out,
+                    double* Q_out, double* prof_out, void* stream);
+
 /* ---- VAE network support (vae_model.py:37-81, BatchNorm1d in train mode) ----
  * Training-mode batch norm over (N, C, L) contiguous activations, bf16 or f32,
  * statistics per channel over N·L < 2³¹ (torch.nn.functional.batch_norm semantics:

@@ -118,6 +118,12 @@ SIGNATURES = {
                                    c_void_p, c_i64, c_void_p, c_void_p]),
     "ocm_decide_f64": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, ctypes.POINTER(OcmDecision), c_void_p,
                                c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "ocm_contrib_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p,
+                                c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "ocm_contrib_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p,
+                                c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     "ocm_bn_scratch_bytes": (ctypes.c_size_t, [c_i32]),
     "ocm_bn_fwd_train": (c_i32, [c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, ctypes.c_float,
                                  ctypes.c_float, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,

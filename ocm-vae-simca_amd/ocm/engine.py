@@ -372,6 +372,40 @@ def decide(T2: torch.Tensor, Q: torch.Tensor, decision: OcmDecision, want_red=Tr
     return t2r, qr, dr
 
 
+def contributions(X, rows: torch.Tensor | None, m: int, P64: torch.Tensor, mean64: torch.Tensor,
+                  inv_diag: torch.Tensor, group: torch.Tensor | None = None, ngroups: int = 1, want_E=False,
+                  want_C=False, want_rows=True, want_profiles=True) -> dict:
+    """Contribution plots of the processed rows (ocm_contrib_f32 / _f64): the
+    residual ``E`` (e_j, Σ_j e_j² = Q) and the T² shares ``C`` (Σ_j c_j = T²) as
+    (m, p) matrices in the input dtype when asked for, their row sums ``Q`` /
+    ``T2``, and ``profiles`` (ngroups, 2, p) float64: Σ_rows e_j² then Σ_rows c_j
+    of the rows of each group (``group``: uint8 device tensor of m ids in
+    [0, ngroups), None: one group).  Without the matrices the call writes
+    O(m + p) values.  A lazy ``PrepView`` is materialised first
+    (ocm_prep_apply_f32) and read by the plain kernel.  Returns device tensors."""
+    X = _plain(X)
+    if isinstance(X, PrepView):
+        X, rows = X.materialize(rows), None
+    k, p = P64.shape
+    dev = X.device
+    f64 = X.dtype == torch.float64
+    vdt = torch.float64 if f64 else torch.float32
+    if group is not None:
+        if group.dtype != torch.uint8 or group.numel() != m or not group.is_contiguous():
+            raise ValueError("contributions: group must be a contiguous uint8 tensor of m ids")
+    E = torch.empty((m, p), dtype=vdt, device=dev) if want_E else None
+    C = torch.empty((m, p), dtype=vdt, device=dev) if want_C else None
+    T2 = torch.empty(m, dtype=torch.float64, device=dev) if want_rows else None
+    Q = torch.empty(m, dtype=vdt, device=dev) if want_rows else None
+    prof = torch.empty((ngroups, 2, p), dtype=torch.float64, device=dev) if want_profiles else None
+    ctx = Context.get(dev.index)
+    fn = "ocm_contrib_f64" if f64 else "ocm_contrib_f32"
+    check(getattr(_lib.load(), fn)(ctx.handle, ptr(X), X.stride(0), ptr(rows), m, p, ptr(P64), ptr(mean64),
+                                   ptr(inv_diag), k, ptr(group), ngroups, ptr(E), p, ptr(C), p, ptr(T2), ptr(Q),
+                                   ptr(prof), _stream(dev)), fn)
+    return {"E": E, "C": C, "T2": T2, "Q": Q, "profiles": prof}
+
+
 def confusion_counts(accept: torch.Tensor, positive: torch.Tensor, stride: int = 1) -> torch.Tensor:
     """{TP, TN, FP, FN} (int64, device) of a 0/1 prediction column ``accept``
     (float64, read at ``stride``) against the uint8 mask ``positive``."""

@@ -52,6 +52,8 @@ Documented deviations:
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -63,7 +65,19 @@ from ocm.prepview import PrepView
 from ocm.replica import gather_rows, replicated_group
 from ocm.synth import shard_bounds
 
-__all__ = ["SIMCA"]
+__all__ = ["SIMCA", "ContributionResult"]
+
+
+@dataclass
+class ContributionResult:
+    """What ``SIMCA.contributions`` returns (NumPy arrays or device tensors)."""
+    Q: object
+    T2: object
+    q_profile: object
+    t2_profile: object
+    counts: object
+    E: object = None
+    C: object = None
 
 
 class _Lazy:
@@ -368,6 +382,98 @@ class SIMCA(BaseEstimator, ClassifierMixin):
                     print(f"Confusion Matrix for class {cls}:\nTP: {mt['TP']}, TN: {mt['TN']}, FP: {mt['FP']}, FN: {mt['FN']}")
                     print(f"Class {cls} - Sensitivity: {mt['sensitivity']}, Specificity: {mt['specificity']:.4f}, "
                           f"Accuracy: {mt['accuracy']:.4f}, Efficiency: {mt['efficiency']:.4f}")
+        return out
+
+    # ------------------------------------------------- explaining a decision
+    def decision_function(self, X):
+        """(m, C) float64: column i is ``D_limit_i − dred_i``, with ``dred`` the
+        reduced distance ``predict`` thresholds (utils/SIMCA.py:131-145, types
+        sim / alt / ci / dd), so ``predict(X)[:, i] == (decision_function(X)[:, i] > 0)``
+        row for row.  NumPy in, NumPy out; tensor or lazy view in, device tensor
+        out; a row-sharded model scores and gathers as ``predict`` does."""
+        shard = self._score_shard(X)
+        Xd = engine.as_device_x(X if shard is None else X[shard[0]:shard[1]])
+        m = Xd.shape[0]
+        C = len(self.model_class)
+        out = torch.zeros((m, C), dtype=torch.float64, device=Xd.device)
+        for i, cls in enumerate(self.model_class):
+            fit = self._fits[cls]
+            info = self._model[cls]
+            dec = self._decision(info["T2_limit"], info["Q_limit"], info["D_limit"])
+            if m == 0:  # a rank without rows of a sharded call
+                continue
+            sc = engine.score(Xd, None, m, fit.P64, fit.mean64, fit.inv_diag)
+            _, _, dred = engine.decide(sc["T2"], sc["Q"], dec, want_red=False, want_dred=True)
+            out[:, i] = dec.dlim - dred
+        if shard is not None:
+            out = gather_rows(out, shard[2])
+        return out if _is_dev(X) else out.cpu().numpy()
+
+    def contributions(self, X, cls=None, groups=None, matrices=False):
+        """Contribution plots of class ``cls`` (default: the only class) for the
+        rows of X, extending utils/SIMCA.py:67-71: the residual
+        ``e = (x − μ) − Pᵀt`` (Σ_j e_j² = Q) and the per-variable T² share
+        ``c_j = y_j · Σ_c (t_c/λ_c)·P_cj`` (Σ_j c_j = T²), from one pass over X.
+
+        ``groups`` picks the rows whose profiles are summed together: None (one
+        group), ``"decision"`` (group 0: the rows ``cls`` accepts, group 1: the
+        rows it rejects, from the fused decision of one scoring launch) or an
+        integer array of m ids in [0, G), G ≤ 4.  Returns a
+        ``ContributionResult``: ``Q``, ``T2`` (m,), ``q_profile`` / ``t2_profile``
+        (G, p) float64 sums of e_j² / c_j over the rows of each group,
+        ``counts`` (G,), and ``E`` / ``C`` (m, p) in the input's arithmetic when
+        ``matrices=True`` (else None).  NumPy in, NumPy out; tensor or lazy view
+        in, device tensors out.
+
+        Under a process group the call is per-process: every rank computes the
+        rows it was given, with no collective and no fingerprint exchange."""
+        classes = list(self.model_class)
+        if cls is None:
+            if len(classes) != 1:
+                raise ValueError(f"contributions: the model has {len(classes)} classes, name one (cls=...)")
+            cls = classes[0]
+        if cls not in self._fits:
+            raise ValueError(f"contributions: unknown class {cls!r} (model classes: {classes})")
+        m = int(X.shape[0])
+        gid, G = None, 1
+        if isinstance(groups, str):
+            if groups != "decision":
+                raise ValueError(f"contributions: groups={groups!r} (None, 'decision' or an integer array)")
+            G = 2
+        elif groups is not None:
+            gid = _host_labels(groups)
+            if gid.shape != (m,):
+                raise ValueError(f"contributions: groups has shape {gid.shape}, X has {m} rows")
+            if not np.issubdtype(gid.dtype, np.integer):
+                raise ValueError("contributions: groups must hold integer ids")
+            if m and (gid.min() < 0 or gid.max() >= 4):
+                raise ValueError("contributions: group ids must lie in [0, 4)")
+            G = int(gid.max()) + 1 if m else 1
+        fit = self._fits[cls]
+        info = self._model[cls]
+        Xd = engine.as_device_x(X)  # a lazy view: scored in its fused load path, materialised by the engine
+        dev = Xd.device
+        if groups is None:
+            gdev = None
+        elif gid is not None:
+            gdev = torch.from_numpy(np.ascontiguousarray(gid).astype(np.uint8)).to(dev)
+        else:
+            dec = self._decision(info["T2_limit"], info["Q_limit"], info["D_limit"])
+            acc = torch.empty(m, dtype=torch.float64, device=dev)
+            engine.score(Xd, None, m, fit.P64, fit.mean64, fit.inv_diag, want_T2=False, want_Q=False, decision=dec,
+                         accept_out=acc, accept_stride=1)
+            gdev = (acc == 0).to(torch.uint8)
+        res = engine.contributions(Xd, None, m, fit.P64, fit.mean64, fit.inv_diag, group=gdev, ngroups=G,
+                                   want_E=matrices, want_C=matrices)
+        counts = torch.bincount(gdev.to(torch.int64), minlength=G) if gdev is not None else \
+            torch.full((1,), m, dtype=torch.int64, device=dev)
+        out = ContributionResult(Q=res["Q"], T2=res["T2"], q_profile=res["profiles"][:, 0, :],
+                                 t2_profile=res["profiles"][:, 1, :], counts=counts, E=res["E"], C=res["C"])
+        if not _is_dev(X):
+            for name in ("Q", "T2", "q_profile", "t2_profile", "counts", "E", "C"):
+                v = getattr(out, name)
+                if v is not None:
+                    setattr(out, name, _np(v))
         return out
 
     # -------------------------------------------------------------- metrics
