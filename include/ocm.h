@@ -381,6 +381,32 @@ int ocm_prep_rowstats_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, 
  * shapes and modes the fused kernels do not cover and for tests. */
 int ocm_prep_apply_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
                        const ocm_prep* prep, float* out, int64_t ldo, void* stream);
+/* ---- scatter correction against a reference spectrum (MSC, EMSC) ----
+ * Basis B: q × p fp64, 2 ≤ q ≤ 8 and p ≥ q: row 0 all ones, row 1 the reference spectrum, rows 2.. the
+ * baseline (polynomials in λ ∈ [−1, 1]) and interferent terms.  Weights W = pinv(Bᵀ), q × p fp64, from
+ * the host (ocm/preprocess.py scatter_weights).  Row coefficients c = W·x: c0 the offset, c1 the scale,
+ * c2.. the baseline amplitudes — the least-squares fit x ≈ Σ_t c_t·B_t.
+ *   MSC  (q = 2, = np.polyfit(ref, x, 1)):  y_j = (x_j − c0) / c1
+ *   EMSC:                                   y_j = (x_j − c0 − Σ_{t≥2} c_t·B_tj) / c1
+ * No epsilon is added to c1: a row orthogonal to the reference gives inf / nan, as NumPy does.
+ * Numerics: the q dot products are fp64 sums of (double)x_j·W_tj in a fixed order (no atomics: the same
+ * bits on every launch); coefficients are the fp64 results rounded to float32.  The row-affine pair of a
+ * lazy view (ocm_prep.rowstat with snv = 1) is m_r = (float)c0, s_r = (float)(1.0 / c1), so the view's
+ * y_j = (x_j − m_r)·s_r is MSC.  ocm_emsc_apply_f32 then works in float32, in this order:
+ *   u = x_j − m_r;  for t = 2, 3, .., q − 1:  u = fmaf(−(float)c_t, (float)B_tj, u);  y_j = u·s_r
+ * (the product never fused into a later operation), which for q = 2 is what ocm_prep_apply_f32 writes for
+ * the MSC view of the same rows, bit for bit.
+ * X [dev] m × p float32, any ldx ≥ p and any 4-byte alignment (16-byte aligned rows, W and B with
+ * p % 4 == 0 and p ≤ 4096 (p ≤ 2048 when q > 4) take the vector path: the row stays in registers); W, B
+ * [dev] q × p fp64,
+ * dense (B may be NULL when q = 2).  OCM_ERR_ARG for q < 2, q > 8 or p < q. */
+/* One read-only pass over X.  coef_out [dev] m × q floats (nullable), rowstat_out [dev] m × 2 floats
+ * (m_r, s_r) (nullable); at least one of them. */
+int ocm_rowfit_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, const double* W, int32_t q,
+                   float* coef_out, float* rowstat_out, void* stream);
+/* One read and one write of X: out [dev] m × p (ldo ≥ p) = the corrected rows; coef_out as above (nullable). */
+int ocm_emsc_apply_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, const double* W,
+                       const double* B, int32_t q, float* out, int64_t ldo, float* coef_out, void* stream);
 /* ocm_colmean_f32 / ocm_gram_f32_ex / ocm_score_f32_diag on the preprocessed rows, read raw from X.
  * The default i8×3 Gram applies the transform in its quantiser (halo columns staged through LDS) and
  * k_score_1p applies it to each row tile in registers as the tile arrives (p ∈ {256, 512, 1024, 2048},

@@ -28,7 +28,8 @@ from . import _lib, engine
 from ._lib import Context, check, ptr
 from .prepview import PrepView
 
-__all__ = ["savgol_taps", "snv_savgol", "snv", "savgol_filter", "mahalanobis_outlier_mask", "PrepView"]
+__all__ = ["savgol_taps", "snv_savgol", "snv", "savgol_filter", "mahalanobis_outlier_mask", "PrepView",
+           "MSC", "EMSC", "scatter_basis", "scatter_weights"]
 
 
 @functools.lru_cache(maxsize=64)
@@ -103,6 +104,222 @@ def snv(X, out=None) -> torch.Tensor:
 def savgol_filter(X, window_length, polyorder, deriv=0, delta=1.0, out=None) -> torch.Tensor:
     """scipy.signal.savgol_filter(X, ..., axis=1, mode='interp') on the GPU."""
     return snv_savgol(X, window_length, polyorder, deriv, delta, snv=False, out=out)
+
+
+SCATTER_QMAX = 8  # rows of the EMSC basis the kernels take (include/ocm.h)
+
+
+def scatter_basis(reference, degree: int = 0, wavelengths=None, interferents=None) -> np.ndarray:
+    """The (q, p) fp64 basis of MSC / EMSC (include/ocm.h, scatter correction):
+    row 0 ones, row 1 the reference spectrum, then λ¹..λ^degree with
+    λ = linspace(−1, 1, p) (``wavelengths``, if given, mapped affinely to
+    [−1, 1]), then the interferent spectra.  ``degree=0`` without
+    interferents is the MSC basis.  A pure host function (no device)."""
+    ref = np.asarray(reference, dtype=np.float64)
+    if ref.ndim != 1 or ref.size < 1:
+        raise ValueError("scatter correction: the reference must be a 1-D spectrum")
+    p = ref.size
+    if not np.isfinite(ref).all():
+        raise ValueError("scatter correction: the reference has non-finite values")
+    degree = int(degree)
+    if degree < 0:
+        raise ValueError("scatter correction: degree must be >= 0")
+    inter = np.zeros((0, p)) if interferents is None else np.atleast_2d(np.asarray(interferents, dtype=np.float64))
+    if inter.ndim != 2 or inter.shape[1] != p:
+        raise ValueError(f"scatter correction: interferents must have {p} columns, like the reference")
+    q = 2 + degree + inter.shape[0]
+    if q > SCATTER_QMAX:
+        raise ValueError(f"scatter correction: the basis has q = {q} rows (ones, reference, {degree} polynomial, "
+                         f"{inter.shape[0]} interferent); at most {SCATTER_QMAX} are supported")
+    if p < q:
+        raise ValueError(f"scatter correction: p = {p} columns cannot determine q = {q} coefficients")
+    if np.ptp(ref) == 0.0:
+        raise ValueError("scatter correction: the reference spectrum is constant (collinear with the offset term)")
+    if wavelengths is None:
+        lam = np.linspace(-1.0, 1.0, p)
+    else:
+        wl = np.asarray(wavelengths, dtype=np.float64)
+        if wl.shape != (p,):
+            raise ValueError(f"scatter correction: wavelengths must have length {p}, like the reference")
+        lo, hi = float(wl.min()), float(wl.max())
+        if not (np.isfinite(wl).all() and hi > lo):
+            raise ValueError("scatter correction: wavelengths must be finite and not all equal")
+        lam = (2.0 * wl - (hi + lo)) / (hi - lo)
+    rows = [np.ones(p), ref] + [lam ** d for d in range(1, degree + 1)] + list(inter)
+    return np.ascontiguousarray(np.stack(rows), dtype=np.float64)
+
+
+def scatter_weights(basis) -> np.ndarray:
+    """W = pinv(Bᵀ), (q, p) fp64: ``W @ x`` are the least-squares coefficients
+    of x on the rows of B (for the MSC basis: ``np.polyfit(ref, x, 1)[::-1]``).
+    The rows of B are scaled to unit norm for the pseudo-inverse (the
+    reference's level does not enter the conditioning) and the scaling is
+    undone on W.  A pure host function (no device)."""
+    B = np.asarray(basis, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] < 2 or B.shape[0] > SCATTER_QMAX or B.shape[1] < B.shape[0]:
+        raise ValueError(f"scatter correction: the basis must be (q, p) with 2 <= q <= {SCATTER_QMAX} and p >= q")
+    norm = np.linalg.norm(B, axis=1)
+    if not (np.isfinite(norm).all() and (norm > 0).all()):
+        raise ValueError("scatter correction: the basis has a zero or non-finite row")
+    Bn = B / norm[:, None]
+    if np.linalg.matrix_rank(Bn.T) < B.shape[0]:
+        raise ValueError("scatter correction: the basis rows are linearly dependent")
+    return np.ascontiguousarray(np.linalg.pinv(Bn.T) / norm[:, None], dtype=np.float64)
+
+
+def _weights_key(W: np.ndarray) -> int:
+    from .replica import _array_hash
+
+    return _array_hash(W)
+
+
+def _device_rows(X):
+    """A float32 device matrix the scatter kernels read in place: a row slice
+    of a wider tensor keeps its row stride."""
+    if isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and \
+            X.stride(1) == 1 and X.stride(0) >= X.shape[1]:
+        return X
+    Xd = engine.as_device_f32(X)
+    return Xd.materialize() if isinstance(Xd, PrepView) else Xd
+
+
+def _row_statistics(X: torch.Tensor, W_dev: torch.Tensor) -> torch.Tensor:
+    """``ocm_rowfit_f32``: the (m, 2) float32 pairs (m_r, s_r) = (c0, 1/c1) of
+    the rows of a float32 device matrix against the (q, p) fp64 device weights."""
+    m, p = X.shape
+    rs = torch.empty((m, 2), dtype=torch.float32, device=X.device)
+    check(_lib.load().ocm_rowfit_f32(Context.get(X.device.index).handle, ptr(X), X.stride(0), m, p, ptr(W_dev),
+                                     int(W_dev.shape[0]), None, ptr(rs), engine._stream(X.device)), "ocm_rowfit_f32")
+    return rs
+
+
+class EMSC:
+    """Extended multiplicative scatter correction against a reference spectrum
+    (include/ocm.h, scatter correction): each row x is fitted by least squares
+    on the basis ``basis_`` (ones, the reference, λ¹..λ^degree, interferents),
+    c = ``weights_`` @ x in fp64 on the GPU, and
+    y = (x − c0 − Σ_{t≥2} c_t·B_t) / c1.
+
+    ``fit(X, rows=None)`` takes the reference as the fp64 column mean of the
+    training rows unless ``reference=`` was given.  ``transform(X)`` is eager:
+    one read and one write of X (``ocm_emsc_apply_f32``); with
+    ``window_length=`` it then runs ``savgol_filter`` on the result, a second
+    pass over the matrix.  A basis with baseline or interferent rows has no
+    lazy view (the correction depends on the column): ``lazy=True`` raises,
+    use the eager ``transform(X)``; with only the two MSC rows (``degree=0``,
+    no interferents) the weights and every path are those of ``MSC``."""
+
+    def __init__(self, degree: int = 2, reference=None, wavelengths=None, interferents=None):
+        self.degree = int(degree)
+        self.wavelengths = wavelengths
+        self.interferents = interferents
+        n_int = 0 if interferents is None else np.atleast_2d(np.asarray(interferents)).shape[0]
+        if self.degree < 0:
+            raise ValueError("scatter correction: degree must be >= 0")
+        if 2 + self.degree + n_int > SCATTER_QMAX:
+            raise ValueError(f"scatter correction: the basis would have q = {2 + self.degree + n_int} rows; at most "
+                             f"{SCATTER_QMAX} are supported")
+        self.reference_ = self.basis_ = self.weights_ = None
+        self._dev = {}
+        if reference is not None:
+            self._set_reference(reference)
+
+    def _set_reference(self, reference):
+        B = scatter_basis(reference, self.degree, self.wavelengths, self.interferents)
+        W = scatter_weights(B)
+        self.reference_ = B[1].copy()
+        self.basis_, self.weights_ = B, W
+        self._key = _weights_key(W)
+        self._dev = {}
+
+    def _on_device(self, device):
+        """(W, B) as fp64 device tensors, uploaded once per device."""
+        if device not in self._dev:
+            self._dev[device] = (torch.from_numpy(self.weights_).to(device), torch.from_numpy(self.basis_).to(device))
+        return self._dev[device]
+
+    def fit(self, X, rows=None):
+        if self.reference_ is None:
+            Xd = _device_rows(X)
+            if Xd.stride(0) != Xd.shape[1]:
+                Xd = Xd.contiguous()
+            if rows is not None:
+                rows = torch.as_tensor(rows, device=Xd.device).to(torch.int64)
+            n = Xd.shape[0] if rows is None else int(rows.numel())
+            self._set_reference(engine.colmean(Xd, rows, n).cpu().numpy())
+        return self
+
+    def _check(self, X):
+        if self.weights_ is None:
+            raise ValueError(f"{type(self).__name__}: call fit(X) first, or pass reference=")
+        if len(X.shape) != 2 or X.shape[1] != self.reference_.size:
+            raise ValueError(f"{type(self).__name__}: X must be (m, {self.reference_.size}) like the reference, got "
+                             f"{tuple(X.shape)}")
+
+    def _eager(self, Xd):
+        m, p = Xd.shape
+        W, B = self._on_device(Xd.device)
+        out = torch.empty((m, p), dtype=torch.float32, device=Xd.device)
+        check(_lib.load().ocm_emsc_apply_f32(Context.get(Xd.device.index).handle, ptr(Xd), Xd.stride(0), m, p, ptr(W),
+                                             ptr(B), int(W.shape[0]), ptr(out), p, None,
+                                             engine._stream(Xd.device)), "ocm_emsc_apply_f32")
+        return out
+
+    def _view(self, Xd, window_length, polyorder, deriv, delta, through):
+        """The lazy MSC view: the row statistics come from ocm_rowfit_f32 here,
+        the consumers apply (x − m_r)·s_r and the filter in their load paths."""
+        # the fit reads the rows where they are, as the eager pass does (both then sum in the same order)
+        rs = _row_statistics(Xd, self._on_device(Xd.device)[0])
+        if Xd.stride(0) != Xd.shape[1]:
+            Xd = Xd.contiguous()
+        tp =savgol_taps(int(window_length), int(polyorder), int(deriv), float(delta)) if window_length else None
+        return PrepView(Xd, window_length, polyorder, deriv, delta, False, tp, through=through, rowstat=rs,
+                        kind="msc", stat_key=self._key)
+
+    def transform(self, X, window_length: int | None = None, polyorder: int = 2, deriv: int = 0, delta: float = 1.0,
+                  lazy=False):
+        """The corrected rows as a float32 device tensor (``lazy=False``), or
+        — for a basis of the two MSC rows only — a ``PrepView``
+        (``lazy=True`` / ``"write"``, as ``snv_savgol`` returns).  With
+        ``window_length`` the Savitzky–Golay filter follows the correction."""
+        self._check(X)
+        if lazy not in (False, True, "write"):
+            raise ValueError(f'{type(self).__name__}.transform: lazy must be False, True or "write"')
+        p = self.reference_.size
+        if window_length is not None:
+            if int(window_length) > p:
+                raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+            savgol_taps(int(window_length), int(polyorder), int(deriv), float(delta))  # validates the filter
+        q = self.basis_.shape[0]
+        if lazy and q > 2:
+            raise ValueError(f"{type(self).__name__}.transform: a basis with baseline or interferent rows (q = {q}) "
+                             "has no lazy view, its correction depends on the column; use the eager transform(X) "
+                             "(lazy=False), or MSC / EMSC(degree=0) for a lazy view")
+        Xd = _device_rows(X)
+        if lazy:
+            return self._view(Xd, window_length, polyorder, deriv, delta, lazy == "write")
+        if window_length is None:
+            return self._eager(Xd)
+        if q == 2:  # one pass: the view's formula, written out
+            return self._view(Xd, window_length, polyorder, deriv, delta, False).materialize()
+        return savgol_filter(self._eager(Xd), window_length, polyorder, deriv, delta)
+
+
+class MSC(EMSC):
+    """Multiplicative scatter correction: y = (x − a_r) / b_r with
+    (b_r, a_r) = ``np.polyfit(reference, x, 1)``, the fit in fp64 on the GPU.
+
+    ``transform(X)`` is one read and one write of X (``ocm_emsc_apply_f32``,
+    q = 2); with ``window_length=`` the Savitzky–Golay filter runs in the
+    same pass (the materialised view).  ``lazy=True`` returns a ``PrepView``
+    the SIMCA fit / predict / transform, the CV engine and the engine entry
+    points read in place, as they read an SNV view: only the (m, 2) row
+    statistics are computed here (``ocm_rowfit_f32``, one read of X).
+    ``lazy="write"`` is the write-through view.  Eager and lazy values are
+    bit-identical."""
+
+    def __init__(self, reference=None):
+        super().__init__(degree=0, reference=reference)
 
 
 def mahalanobis_outlier_mask(X, n_components: int, percentile: float = 95.0, rows=None):

@@ -49,11 +49,19 @@ def materialised_count(device: int | None = None) -> int:
 
 
 class PrepView:
-    """SNV (optional) then Savitzky–Golay (optional) of the rows of ``X``,
-    evaluated lazily inside the kernels that consume it."""
+    """A row-affine scatter correction (optional) then Savitzky–Golay
+    (optional) of the rows of ``X``, evaluated lazily inside the kernels that
+    consume it.  The row-affine part ``(x − m_r)·s_r`` is the SNV (``snv=True``:
+    the row's own moments, computed on first use) or any correction whose
+    per-row pair the caller supplies: ``rowstat`` is a (m, 2) float32 device
+    tensor of ``(m_r, s_r)``, ``kind`` its label (``"msc"``: the fit against a
+    reference spectrum, ``ocm.preprocess.MSC``) and ``stat_key`` an integer
+    that identifies where the pairs came from (a hash of the MSC weights),
+    which ``ocm.replica`` puts into the view's fingerprint."""
 
     def __init__(self, X: torch.Tensor, window_length: int | None, polyorder: int, deriv: int, delta: float,
-                 snv: bool, taps64=None, through: bool = False):
+                 snv: bool, taps64=None, through: bool = False, rowstat: torch.Tensor | None = None,
+                 kind: str | None = None, stat_key: int = 0):
         if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2):
             raise TypeError("PrepView wraps a 2-D float32 CUDA tensor")
         if X.stride(1) != 1:
@@ -64,11 +72,23 @@ class PrepView:
         self.deriv = int(deriv) if self.window else 0
         self.delta = float(delta)
         self.snv = bool(snv)
-        if not self.window and not self.snv:
-            raise ValueError("PrepView: nothing to apply (no SNV and no filter)")
+        if rowstat is not None:
+            if self.snv:
+                raise ValueError("PrepView: precomputed row statistics and snv=True exclude each other")
+            if not (isinstance(rowstat, torch.Tensor) and rowstat.dtype == torch.float32 and rowstat.device == X.device
+                    and tuple(rowstat.shape) == (X.shape[0], 2)):
+                raise TypeError("PrepView: rowstat must be a (m, 2) float32 tensor on X's device")
+            if not kind:
+                raise ValueError("PrepView: precomputed row statistics need a kind label")
+        elif kind not in (None, "snv" if self.snv else "none"):
+            raise ValueError(f"PrepView: kind={kind!r} needs its row statistics (rowstat=)")
+        self.kind = str(kind) if rowstat is not None else ("snv" if self.snv else "none")
+        self.stat_key = int(stat_key)
+        if not self.window and not self.snv and rowstat is None:
+            raise ValueError("PrepView: nothing to apply (no scatter correction and no filter)")
         self._taps = (torch.from_numpy(taps64).to(torch.float32).to(X.device)
                       if self.window else None)
-        self._rowstat = None
+        self._rowstat = rowstat.contiguous() if rowstat is not None else None
         self.through = bool(through)
         self._xp = None  # X′ once a write-through Gram has formed it
 
@@ -113,15 +133,16 @@ class PrepView:
         return self.X.stride() if d is None else self.X.stride(d)
 
     def __repr__(self):
-        return (f"PrepView(shape={tuple(self.shape)}, snv={self.snv}, window={self.window or None}, "
-                f"polyorder={self.polyorder}, deriv={self.deriv}, through={self.through}, "
-                f"written={self._xp is not None})")
+        return (f"PrepView(shape={tuple(self.shape)}, kind={self.kind!r}, snv={self.snv}, "
+                f"window={self.window or None}, polyorder={self.polyorder}, deriv={self.deriv}, "
+                f"through={self.through}, written={self._xp is not None})")
 
     # ---- the transform ----
     def rowstat(self) -> torch.Tensor | None:
-        """(m_r, s_r) per row (SNV only): one read-only pass over X, computed
-        once per view (ocm_prep_rowstats_f32)."""
-        if not self.snv:
+        """(m_r, s_r) per row, or None without a scatter correction.  SNV: one
+        read-only pass over X, computed once per view (ocm_prep_rowstats_f32);
+        other kinds: the pairs the view was built with."""
+        if self._rowstat is None and not self.snv:
             return None
         if self._rowstat is None:
             m, p = self.X.shape
@@ -134,7 +155,7 @@ class PrepView:
 
     def struct(self) -> OcmPrep:
         rs = self.rowstat()
-        return OcmPrep(self.window, self.deriv, 1 if self.snv else 0, 0,
+        return OcmPrep(self.window, self.deriv, 1 if rs is not None else 0, 0,
                        self._taps.data_ptr() if self._taps is not None else None,
                        rs.data_ptr() if rs is not None else None)
 

@@ -89,7 +89,10 @@ def _rows_hash(X, n: int) -> tuple[int, int]:
 
     extra = b""
     if isinstance(X, PrepView):
-        extra = repr((X.window, X.polyorder, X.deriv, X.delta, X.snv, X.through)).encode()
+        # the kind of row-affine correction and where its row statistics came from (for an MSC view a
+        # hash of the weights, so of the reference spectrum): the raw rows alone do not tell two
+        # views with different references apart
+        extra = repr((X.window, X.polyorder, X.deriv, X.delta, X.snv, X.through, X.kind, X.stat_key)).encode()
         src = X.written() if X.written() is not None else X.X
         code = 3
     else:
