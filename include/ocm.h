@@ -495,6 +495,31 @@ int ocm_contrib_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* r
                     int32_t ngroups, double* E_out, int64_t lde, double* C_out, int64_t ldc, double* T2_out,
                     double* Q_out, double* prof_out, void* stream);
 
+/* ---- object-level sums (an object = a run of adjacent rows) ----
+ * The data sets are objects of many pixel spectra each (nut_data.py:131-185 stores every connected
+ * component as an (n_pixels, p) block); the per-object sums the host loops over `obj_ids == idx`
+ * (utils/data_utils.py:79-82) form, in one read of X:
+ *   sum_out[g, j] = Σ_{r = offsets[g]}^{offsets[g+1]−1} (double)X[r·ldx + j]      g < nseg, j < p
+ * offsets [dev] nseg + 1 int64, non-decreasing, 0 ≤ offsets[0], offsets[nseg] ≤ m ((nseg + 1)·8 bytes,
+ *   read by every workgroup from L2).  They are NOT checked here, as `rows` is not: the caller
+ *   validates them (ocm/objects.py check_offsets).  Offsets that break the contract give wrong sums but
+ *   no access outside X, sum_out or the workspace: row reads are bounded by m and segment indices by
+ *   nseg in the kernels.
+ * X [dev] m × p float32 / float64, any ldx ≥ p; rows outside [offsets[0], offsets[nseg]) and columns
+ *   ≥ p of a strided X are never read.  Loads are 16 bytes per lane when p, ldx and the base allow
+ *   (p % 4 == 0, ldx % 4 == 0, 16-byte aligned; float64: % 2), else 8 or 4 (float64: 8).
+ * sum_out [dev] nseg × ld_out doubles (ld_out ≥ p; nseg·p·8 bytes written, columns ≥ p untouched); an
+ *   empty segment gives exactly 0.0.
+ * Numerics: fp64 accumulation; the summation order is a function of the offsets alone (rows in order
+ *   inside each 256-row chunk at multiples of 256, then a segment's chunk partials in chunk order,
+ *   aligned groups of 64 chunks summed first), no floating-point atomics: two calls give the same bits.
+ * Workspace: (2 + 1/64)·(m/256 + 1)·p doubles (134 MB at 1M × 2048), written only where a segment
+ *   crosses a chunk boundary.  nseg = 0 is a no-op; m = 0 writes zeros.  OCM_ERR_ARG for m ≥ 2^31. */
+int ocm_segsum_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, const int64_t* offsets,
+                   int64_t nseg, double* sum_out, int64_t ld_out, void* stream);
+int ocm_segsum_f64(ocm_ctx* ctx, const double* X, int64_t ldx, int64_t m, int32_t p, const int64_t* offsets,
+                   int64_t nseg, double* sum_out, int64_t ld_out, void* stream);
+
 /* ---- VAE network support (vae_model.py:37-81, BatchNorm1d in train mode) ----
  * Training-mode batch norm over (N, C, L) contiguous activations, bf16 or f32,
  * statistics per channel over N·L < 2³¹ (torch.nn.functional.batch_norm semantics:

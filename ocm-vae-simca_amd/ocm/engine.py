@@ -406,6 +406,49 @@ def contributions(X, rows: torch.Tensor | None, m: int, P64: torch.Tensor, mean6
     return {"E": E, "C": C, "T2": T2, "Q": Q, "profiles": prof}
 
 
+def segment_sums(X, offsets, checked: bool = False) -> torch.Tensor:
+    """(G, p) float64 device tensor of the column sums of rows
+    [offsets[g], offsets[g + 1]) of X (ocm_segsum_f32 / _f64: one read of X, fp64
+    accumulation, a fixed order; an empty segment gives zeros).  X: a float32 or
+    float64 device matrix with row stride ≥ p; a row slice of a wider tensor is
+    read in place.  A lazy ``PrepView`` is materialised first (ocm_prep_apply_f32):
+    the mean of preprocessed rows is not the preprocessing of the mean, so there
+    is no lazy form.  ``offsets``: G + 1 non-decreasing row offsets, host
+    array-like or an int64 device tensor; they are validated on the host
+    (``ocm.objects.check_offsets``; the kernels do not check them) unless the
+    caller says it has (``checked=True``)."""
+    from .objects import check_offsets
+
+    X = _plain(X)
+    if isinstance(X, PrepView):
+        X = X.materialize()
+    if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and
+            X.dtype in (torch.float32, torch.float64)):
+        raise ValueError("segment_sums: X must be a 2-D float32 or float64 device tensor")
+    m, p = X.shape
+    if p == 0:
+        raise ValueError("segment_sums: X has no columns")
+    if (p > 1 and X.stride(1) != 1) or (m > 1 and X.stride(0) < p):
+        X = X.contiguous()
+    ldx = X.stride(0) if m > 1 else p
+    dev = X.device
+    if isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.dtype == torch.int64:
+        if not checked:
+            check_offsets(offsets, m)
+        off = offsets.to(dev).contiguous()
+        if off.dim() != 1 or off.numel() < 1:
+            raise ValueError("segment_sums: offsets must be a 1-D tensor of G + 1 >= 1 row offsets")
+    else:
+        off = torch.from_numpy(offsets if checked and isinstance(offsets, np.ndarray) and
+                               offsets.dtype == np.int64 else check_offsets(offsets, m)).to(dev)
+    G = off.numel() - 1
+    out = torch.empty((G, p), dtype=torch.float64, device=dev)
+    fn = "ocm_segsum_f64" if X.dtype == torch.float64 else "ocm_segsum_f32"
+    check(getattr(_lib.load(), fn)(Context.get(dev.index).handle, ptr(X), ldx, m, p, ptr(off), G, ptr(out), p,
+                                   _stream(dev)), fn)
+    return out
+
+
 def confusion_counts(accept: torch.Tensor, positive: torch.Tensor, stride: int = 1) -> torch.Tensor:
     """{TP, TN, FP, FN} (int64, device) of a 0/1 prediction column ``accept``
     (float64, read at ``stride``) against the uint8 mask ``positive``."""

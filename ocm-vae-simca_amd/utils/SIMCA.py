@@ -65,7 +65,7 @@ from ocm.prepview import PrepView
 from ocm.replica import gather_rows, replicated_group
 from ocm.synth import shard_bounds
 
-__all__ = ["SIMCA", "ContributionResult"]
+__all__ = ["SIMCA", "ContributionResult", "ObjectResult"]
 
 
 @dataclass
@@ -78,6 +78,24 @@ class ContributionResult:
     counts: object
     E: object = None
     C: object = None
+
+
+@dataclass
+class ObjectResult:
+    """What ``SIMCA.predict_objects`` returns: (G, C) float64 arrays (NumPy or
+    device tensors), columns in ``model_class`` order as in ``predict``.
+    ``pred`` 0/1 per object and class; ``score`` the object's distance to the
+    limit (positive: accepted); ``fraction`` the share of accepted pixels (None
+    for rule "mean_spectrum"); ``counts`` (G,) int64 rows per object;
+    ``metrics`` {class: object-level rates} when ``y_true`` was given."""
+    pred: object
+    score: object
+    fraction: object
+    counts: object
+    metrics: object = None
+
+
+OBJECT_RULES = ("vote", "mean_distance", "mean_spectrum")
 
 
 class _Lazy:
@@ -475,6 +493,91 @@ class SIMCA(BaseEstimator, ClassifierMixin):
                 if v is not None:
                     setattr(out, name, _np(v))
         return out
+
+    # ------------------------------------------------------ object decisions
+    def predict_objects(self, X, objects=None, offsets=None, rule="vote", min_fraction=0.5, y_true=None):
+        """Decisions per object, an object being a run of adjacent rows of X
+        (the pixels of one nut).  Exactly one of ``objects`` (m ids, one per
+        row; runs of equal ids are the objects, in order of appearance) and
+        ``offsets`` (G + 1 row offsets) is given; every row belongs to an
+        object (offsets[0] = 0, offsets[G] = m) and no object is empty.
+
+        ``rule``:
+          "vote"           one pixel scoring pass (``decision_function``), the
+                           accept matrix D > 0 (``predict``'s, row for row) and
+                           one segment sum over each (m, C) matrix;
+                           ``fraction`` = accepted pixels / count, ``score`` =
+                           mean of D over the object, ``pred`` = fraction ≥
+                           ``min_fraction`` (in (0, 1]);
+          "mean_distance"  the same sums, ``pred`` = score > 0;
+          "mean_spectrum"  ``predict`` and ``decision_function`` of the (G, p)
+                           object means (``ocm.objects.object_means``: a lazy
+                           view is materialised first); ``fraction`` is None.
+
+        Returns an ``ObjectResult``.  With ``y_true`` of shape (G,),
+        ``result.metrics[cls]`` holds the object-level rates; ``self.metrics`` is
+        not touched.  NumPy in, NumPy out; tensor or lazy view in, device
+        tensors out.  Under a process group the call is per-process: every rank
+        computes the rows it was given, with no collective and no fingerprint
+        exchange."""
+        from ocm import objects as _objects
+        from ocm.replica import per_process
+
+        m = int(X.shape[0])
+        if (objects is None) == (offsets is None):
+            raise ValueError("predict_objects: give exactly one of objects= (m ids) and offsets= (G + 1 row offsets)")
+        if rule not in OBJECT_RULES:
+            raise ValueError(f"predict_objects: rule={rule!r} (one of {', '.join(OBJECT_RULES)})")
+        if not 0.0 < float(min_fraction) <= 1.0:
+            raise ValueError(f"predict_objects: min_fraction={min_fraction!r} must lie in (0, 1]")
+        if objects is not None:
+            ids = _host_labels(objects)
+            if ids.shape != (m,):
+                raise ValueError(f"predict_objects: objects has shape {ids.shape}, X has {m} rows")
+            off = _objects.segment_offsets(ids)
+        else:
+            off = _objects.check_offsets(offsets, m)
+            if off[0] != 0 or off[-1] != m:
+                raise ValueError(f"predict_objects: every row belongs to an object: offsets must run from 0 to {m}, "
+                                 f"got {int(off[0])} to {int(off[-1])}")
+        counts = np.diff(off)
+        if (counts == 0).any():
+            raise ValueError(f"predict_objects: object {int(np.flatnonzero(counts == 0)[0])} is empty")
+        G = counts.size
+        yt = None
+        if y_true is not None:
+            yt = _host_labels(y_true)
+            if yt.shape != (G,):
+                raise ValueError(f"predict_objects: y_true has shape {yt.shape}, there are {G} objects")
+
+        with per_process():
+            Xd = engine.as_device_x(X)
+            if rule == "mean_spectrum":
+                means = _objects.object_means(Xd, off)
+                pred, score, fraction = self.predict(means), self.decision_function(means), None
+            else:
+                D = self.decision_function(Xd)
+                n = torch.from_numpy(counts.astype(np.float64)).to(D.device)[:, None]
+                off_dev = torch.from_numpy(off).to(D.device)
+                fraction = engine.segment_sums((D > 0).to(torch.float64), off_dev, checked=True) / n
+                score = engine.segment_sums(D, off_dev, checked=True) / n
+                pred = ((fraction >= float(min_fraction)) if rule == "vote" else (score > 0)).to(torch.float64)
+        res = ObjectResult(pred=pred, score=score, fraction=fraction,
+                           counts=torch.from_numpy(counts).to(pred.device))
+        if yt is not None:
+            ph = _np(pred)
+            res.metrics = {}
+            for i, cls in enumerate(self.model_class):
+                pos = yt == cls
+                acc = ph[:, i] == 1
+                res.metrics[cls] = _rates(np.sum(acc & pos), np.sum(~acc & ~pos), np.sum(acc & ~pos),
+                                          np.sum(~acc & pos))
+        if not _is_dev(X):
+            for name in ("pred", "score", "fraction", "counts"):
+                v = getattr(res, name)
+                if v is not None:
+                    setattr(res, name, _np(v))
+        return res
 
     # -------------------------------------------------------------- metrics
     def _metrics_simca_conformity(self, y_true, y_pred, class_index):

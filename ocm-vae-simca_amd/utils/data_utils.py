@@ -13,7 +13,9 @@ from __future__ import annotations
 import numpy as np
 from sklearn.model_selection import train_test_split
 
-__all__ = ["object_aware_splits", "load_ir_ml_mat", "load_nut_objects_h5"]
+from ocm.objects import stack_objects  # (X, offsets) of a list of objects, for SIMCA.predict_objects
+
+__all__ = ["object_aware_splits", "load_ir_ml_mat", "load_nut_objects_h5", "stack_objects"]
 
 
 def _outlier_keep(X_proc: np.ndarray, n_comp: int, outlier_percentile: float):
