@@ -34,10 +34,7 @@ __device__ __forceinline__ float cv_ld(const float* p, int64_t i) { return p[i];
 __device__ __forceinline__ float cv_ld(const bf16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i].bits << 16); }
 __device__ __forceinline__ void cv_st(float* p, int64_t i, float v) { p[i] = v; }
 __device__ __forceinline__ void cv_st(bf16_t* p, int64_t i, float v) {
-  // round to nearest even, NaN kept quiet (torch's float → bfloat16)
-  const uint32_t u = __float_as_uint(v);
-  const uint32_t r = (u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) : u + 0x7fffu + ((u >> 16) & 1u);
-  p[i].bits = (uint16_t)(r >> 16);
+  p[i].bits = (uint16_t)bf16_bits_rne(v);  // round to nearest even, NaN kept quiet (torch's float → bfloat16)
 }
 
 constexpr int CV_T = 256, CV_OG = 4, CV_KMAX = 15, CV_CMAX = 64;

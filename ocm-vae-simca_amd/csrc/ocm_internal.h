@@ -141,6 +141,15 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return v;
 }
 
+// the bf16 bits of a float32: round to nearest even, NaN kept quiet (torch's
+// float → bfloat16 cast).  A NaN whose payload lies in the low 16 bits only
+// would otherwise truncate to ±inf.
+__device__ __forceinline__ uint32_t bf16_bits_rne(float v) {
+  const uint32_t u = __float_as_uint(v);
+  const uint32_t r = (u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) : u + 0x7fffu + ((u >> 16) & 1u);
+  return r >> 16;
+}
+
 // ---- last-workgroup reductions without fences -----------------------------
 // A grid's partial results meet in its last workgroup to finish.  MI355X's
 // eight XCDs keep private L2s and a CU's L1 is never refreshed by other CUs'

@@ -30,10 +30,8 @@ __device__ __forceinline__ float ld_act(const void* p, int dt, int64_t i) {
 }
 
 __device__ __forceinline__ void st_act(void* p, int dt, int64_t i, float v) {
-  if (dt == OCM_DTYPE_BF16) {  // round to nearest even
-    uint32_t u = __float_as_uint(v);
-    if ((u & 0x7f800000u) != 0x7f800000u) u += 0x7fffu + ((u >> 16) & 1u);
-    static_cast<uint16_t*>(p)[i] = (uint16_t)(u >> 16);
+  if (dt == OCM_DTYPE_BF16) {  // round to nearest even, NaN kept quiet
+    static_cast<uint16_t*>(p)[i] = (uint16_t)bf16_bits_rne(v);
   } else {
     static_cast<float*>(p)[i] = v;
   }
@@ -290,11 +288,7 @@ __global__ __launch_bounds__(VT) void k_standardise(const float* __restrict__ x,
 constexpr int AB_T = 1024, AB_CG = 4, AB_RL = AB_T / AB_CG, AB_U = 2;
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t bf_rne(float v) {  // the bf16 bits of v, round to nearest even
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7f800000u) != 0x7f800000u) u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
+__device__ __forceinline__ uint32_t bf_rne(float v) { return bf16_bits_rne(v); }
 template <int ACT>
 __global__ __launch_bounds__(AB_T) void k_act_bias_bwd(const uint16_t* __restrict__ g, const uint16_t* __restrict__ y,
                                                        int B, int N, uint16_t* __restrict__ gy,
