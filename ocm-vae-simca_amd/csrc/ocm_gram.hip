@@ -18,8 +18,10 @@
 //   GT = 128:           4 waves, BK = 32, 64 KiB LDS,  64 accumulators/lane.
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "ocm_gram_map.h"
 #include "ocm_internal.h"
 
 namespace {
@@ -1608,13 +1610,8 @@ __global__ __launch_bounds__(256) void k_gram_fixup(const float* __restrict__ X,
 // ---------------------------------------------------------------------------
 // band shape of the Gram's tile order (tile rows × tile columns); make exp
 // builds override it for A/B
-#ifndef OCM_G8_BAND_R
-#define OCM_G8_BAND_R 4
-#endif
-#ifndef OCM_G8_BAND_C
-#define OCM_G8_BAND_C 8
-#endif
-constexpr int G8_BAND_R = OCM_G8_BAND_R, G8_BAND_C = OCM_G8_BAND_C;
+// (the defaults, 4 × 8, are in ocm_gram_map.h)
+constexpr int G8_BAND_R = ocm_g8::BAND_R, G8_BAND_C = ocm_g8::BAND_C;
 __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
                                                    int nwg, int nblocks, float* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];        // wave-private: row, column scales
@@ -1856,13 +1853,14 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
 }
 
 // ---------------------------------------------------------------------------
-// k_gram8e — k_gram8d's work on the 16×16×64 integer MFMA
-// (v_mfma_i32_16x16x64_i8, 16 cycles) instead of 32×32×32 (32 cycles): 419
+// k_gram8e (persistent, below) and k_gram8w (one item per workgroup: the
+// launch before it, `make exp` builds only, its A/B partner) — k_gram8d's
+// work on the 16×16×64 integer MFMA (v_mfma_i32_16x16x64_i8, 16 cycles) instead of 32×32×32 (32 cycles): 419
 // vs 386 TF in one process (r03q; the chip holds a higher clock on the
 // 16×16 shape).  Same digit planes, 64×64 wave blocks, band order, three
 // int32 sets and f32 running sums, so the partials are bit for bit those of
 // k_gram8d (the int32 sums are exact; each element's f32 flushes run in the
-// same order).  Default launch: a workgroup is one tile's four blocks
+// same order).  Default order: a workgroup item is one tile's four blocks
 // (off-diagonal tiles first, then the diagonal ones packed) and its waves
 // meet at a barrier every two stages — a fragment is then loaded by two
 // waves of one CU at about the same time and the L1 serves one of them
@@ -1881,71 +1879,60 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
 // stages) and so runs 24 + 8 stages in one round.  Not in the headline
 // instantiation: the branch in the unrolled stage loop cost it 3 %
 // (profiles/r05s9_gram_stage_skip_ab.txt).
+#ifdef OCM_G8E_STAMPS  // diagnostic build (make exp): Σ over workgroup items of wave 0's wall-clock stamps (100 MHz)
+// [0] entry → first MFMA can issue (its operands have arrived), [1] last MFMA
+// → the item's end (last flush; the one-item kernel: its stores issued),
+// [2] entry → end, [3] items
+__device__ unsigned long long g8_stamp_acc[4];
+#define G8_STAMP(V) const uint64_t V = __builtin_amdgcn_s_memrealtime()
+#define G8_STAMP_VAR(V) uint64_t V = 0
+#define G8_STAMP_SET(V) V = __builtin_amdgcn_s_memrealtime()
+#define G8_STAMP_SUM(A, B, C, D)                                              \
+  if (threadIdx.x == 0) {                                                     \
+    atomicAdd(&g8_stamp_acc[0], (unsigned long long)((B) - (A)));             \
+    atomicAdd(&g8_stamp_acc[1], (unsigned long long)((D) - (C)));             \
+    atomicAdd(&g8_stamp_acc[2], (unsigned long long)((D) - (A)));             \
+    atomicAdd(&g8_stamp_acc[3], 1ull);                                        \
+  }
+#else
+#define G8_STAMP(V)
+#define G8_STAMP_VAR(V)
+#define G8_STAMP_SET(V)
+#define G8_STAMP_SUM(A, B, C, D)
+#endif
+
+#ifdef OCM_EXP_SELECTORS  // the product launches k_gram8e (below)
 template <bool ALIGNED, int SYNC, bool FRONT = false, bool SKIP = false>
-__global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
+__global__ __launch_bounds__(256, 1) void k_gram8w(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
                                                    int nwg, int nblocks, float* __restrict__ part, int chunk0) {
   __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];      // wave-private: row, column scales
   __shared__ __attribute__((aligned(16))) float runl[4][16][64][4];  // wave-private f32 running sums
 
+  G8_STAMP(t_in);
   const int b = blockIdx.x;
-  const int q8 = total_wg / 8, r8 = total_wg % 8, x8 = b % 8;
   // XCD-aware remap (each XCD a contiguous range of chunks); chunk0 < 0 (A/B
   // only): dispatch order, the eight XCDs on neighbouring tiles of one chunk
-  const int wg = chunk0 < 0 ? b : (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+  const int wg = chunk0 < 0 ? b : ocm_g8::logical_item(total_wg, b);
   const int cl = wg / nwg, chunk = (chunk0 < 0 ? 0 : chunk0) + cl;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int bi = (wg - cl * nwg) * 4 + wave;
   // SYNC > 0: a workgroup barrier every SYNC stages keeps the four waves in
   // step, so the second wave's load of a shared panel fragment finds it in
   // the CU's L1; a wave past the last block then computes a copy of the last
-  // block (never stored) instead of leaving
-  const bool dead = bi >= nblocks;
-  if (dead && SYNC == 0) return;
-  if (dead) bi = nblocks - 1;
-  int ti = -1, tj = 0, wm = 0, wn = 0;
+  // block (never stored) instead of leaving.  ALIGNED (ocm_gram_map.h): a
+  // workgroup's four waves are one off-diagonal tile's four blocks, so each
+  // A and B panel fragment is fetched by two waves of the same CU.
+  int ti, tj, wm, wn;
+  bool dead;
   if (ALIGNED) {
-    // off-diagonal tiles first, in band order, four blocks each: a
-    // workgroup's four waves are one tile's four blocks, so each A and B
-    // panel fragment is fetched by two waves of the same CU (the L1 serves the
-    // second); then the nt diagonal tiles, three blocks each, packed
-    const int noff = 4 * (ntiles - nt);
-    if (bi < noff) {
-      int rem = bi >> 2;
-      wm = (bi >> 1) & 1;
-      wn = bi & 1;
-      for (int u = 0; u < nt && ti < 0; u += G8_BAND_R)
-        for (int v = u; v < nt && ti < 0; v += G8_BAND_C)
-          for (int a = u; a < min(nt, u + G8_BAND_R) && ti < 0; ++a)
-            for (int c = max(v, a + 1); c < min(nt, v + G8_BAND_C); ++c) {
-              if (rem == 0) {
-                ti = a;
-                tj = c;
-                break;
-              }
-              --rem;
-            }
-    } else {
-      const int d = (bi - noff) / 3, r = (bi - noff) - 3 * d;
-      ti = tj = d;
-      wm = (r == 2);
-      wn = (r >= 1);
-    }
+    const ocm_g8::Block k = ocm_g8::block_tile(nt, ntiles, nblocks, wg - cl * nwg, wave);
+    ti = k.ti, tj = k.tj, wm = k.wm, wn = k.wn, dead = k.dead;
+    if (dead && SYNC == 0) return;
   } else {
-    int rem = bi;
-    for (int u = 0; u < nt && ti < 0; u += G8_BAND_R)
-      for (int v = u; v < nt && ti < 0; v += G8_BAND_C)
-        for (int a = u; a < min(nt, u + G8_BAND_R) && ti < 0; ++a)
-          for (int c = max(v, a); c < min(nt, v + G8_BAND_C); ++c) {
-            const int nbk = (a == c) ? 3 : 4;
-            if (rem < nbk) {
-              ti = a;
-              tj = c;
-              wm = (a == c) ? (rem == 2) : (rem >> 1);
-              wn = (a == c) ? (rem >= 1) : (rem & 1);
-              break;
-            }
-            rem -= nbk;
-          }
+    int bi = (wg - cl * nwg) * 4 + wave;
+    dead = bi >= nblocks;
+    if (dead && SYNC == 0) return;
+    if (dead) bi = nblocks - 1;
+    ocm_g8::packed_block(nt, bi, ti, tj, wm, wn);
   }
   const int tile = ti * nt - ti * (ti - 1) / 2 + (tj - ti);
   const int I = ti * Q8T, J = tj * Q8T;
@@ -2056,6 +2043,11 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
   i32x4 F0A[4][3], F0B[4][3], F1A[4][3], F1B[4][3];
 #pragma unroll
   for (int i = 0; i < 24; ++i) load_frag(F0A, F0B, i, 0);
+#ifdef OCM_G8E_STAMPS
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stage-0 operands are here
+#endif
+  G8_STAMP(t_first);
+  G8_STAMP_VAR(t_last);
   for (int blk = 0; blk < nb; ++blk) {
     const int s0 = blk * SPB;
 #pragma unroll
@@ -2068,26 +2060,275 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
       }
       step(F1A, F1B, F0A, F0B, s0 + u + 1, false);
     }
+    G8_STAMP_SET(t_last);
     flush();
   }
 
-  if (dead) return;
-  float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
+  if (!dead) {
+    float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+      for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = wm * 64 + a * 16 + 4 * g4 + e;
-        const int col = wn * 64 + c * 16 + l15;
-        out[row * Q8T + col] = runl[wave][a * 4 + c][lane][e];
+        for (int e = 0; e < 4; ++e) {
+          const int row = wm * 64 + a * 16 + 4 * g4 + e;
+          const int col = wn * 64 + c * 16 + l15;
+          out[row * Q8T + col] = runl[wave][a * 4 + c][lane][e];
+        }
+  }
+  G8_STAMP(t_out);
+  G8_STAMP_SUM(t_in, t_first, t_last, t_out);
+}
+#endif  // OCM_EXP_SELECTORS
+
+// ---------------------------------------------------------------------------
+// k_gram8e — k_gram8w<ALIGNED, SYNC = 2> as a persistent kernel: one workgroup
+// per CU walks its share of the (chunk, tile) items (ocm_gram_map.h: static
+// striding inside each XCD's contiguous range, in the order the one-item
+// launch dispatched them; no counter, nothing to reset, capture-safe).  What
+// a workgroup used to pay around its stage loop now runs beside MFMAs:
+//   * the band walk is done once per workgroup into an LDS table;
+//   * the 24 load slots of an item's last stage (clamped duplicates in
+//     k_gram8w) fetch stage 0 of the workgroup's next item, through that
+//     item's descriptors (scalar selects at that one unrolled position, no
+//     branch in the stage loop);
+//   * the running sums need no zero pass: an item's first flush adds to +0
+//     (fmaf(v, s, +0.f), the same bits as adding to a zeroed sum);
+//   * an item's runl → part stores ride between the MFMAs of the next item's
+//     stage 0 (a second copy of that one stage, chosen by one uniform branch
+//     per scale block), through a buffer descriptor that is empty for a dead
+//     wave: out-of-range buffer stores are dropped.
+// Same integer sums, same f32 flush order per element: bit for bit the
+// partials of k_gram8d/8e.  The four waves take the same items, and their
+// stage and barrier counts come from the chunk alone (workgroup-uniform).
+// SKIP (θ3 trace Gram, 136 items: one per workgroup on this chip): no
+// cross-item prefetch, an item's stage 0 is loaded at its start.
+// ---------------------------------------------------------------------------
+constexpr int G8P_TMAP = 2048;  // off-diagonal tiles in the LDS table (nt ≤ 64); more: walk per item
+template <bool SKIP>
+__global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
+                                                   int nwg, int nblocks, float* __restrict__ part, int chunk0) {
+  __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];      // wave-private: row, column scales
+  __shared__ __attribute__((aligned(16))) float runl[4][16][64][4];  // wave-private f32 running sums
+  __shared__ uint16_t tmap[G8P_TMAP];                                // off-diagonal rank → ti << 8 | tj
+
+  const int noffr = ntiles - nt;
+  const bool tabled = noffr <= G8P_TMAP;
+  if (tabled) {
+    for (int r = threadIdx.x; r < noffr; r += 256) {
+      int a, c;
+      ocm_g8::offdiag_tile(nt, r, a, c);
+      tmap[r] = (uint16_t)(a << 8 | c);
+    }
+    __syncthreads();
+  }
+  const ocm_g8::Slot sl = ocm_g8::slot_of(total_wg, (int)gridDim.x, (int)blockIdx.x);
+  if (sl.count == 0) return;  // workgroup-uniform
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int l15 = lane & 15, g4 = lane >> 4;
+  constexpr int SPB = Q8BLK / 64;  // 64-row stages per scale block (24)
+  const size_t gstride = (size_t)q.P8 * 32;
+  // sub-panel x of the wave's 64 columns: column 16x + l15, group g4 >> 1, half g4 & 1
+  const int voff = (g4 >> 1) * (int)gstride + l15 * 32 + (g4 & 1) * 16;
+  const int sstride = 2 * (int)gstride;
+  // this lane's first output element of a 16×16 sub-block: row 4·g4, column l15
+  const int vout = (4 * g4 * Q8T + l15) * 4;
+  constexpr uint32_t OUT_SPAN = (63 * Q8T + 64) * 4;  // bytes from a 64×64 block's first element to past its last
+
+  // everything of one item this wave needs, all wave-uniform (SGPRs)
+  struct Item {
+    __amdgpu_buffer_rsrc_t ra[3], rb[3];  // digit planes at the A / B panel of the chunk
+    __amdgpu_buffer_rsrc_t rout;          // the 64×64 output block (empty: dead wave)
+    const float *srow, *scol;             // scale rows of the chunk at the A / B panel's first column
+    int nb, nvs;
+  };
+  auto setup = [&](int wg) __attribute__((always_inline)) -> Item {
+    const int cl = wg / nwg, chunk = chunk0 + cl;
+    ocm_g8::Block k = ocm_g8::block_of(nt, ntiles, nblocks, wg - cl * nwg, wave);
+    if (k.offrank >= 0) {
+      if (tabled) {
+        const int v = __builtin_amdgcn_readfirstlane((int)tmap[k.offrank]);
+        k.ti = v >> 8;
+        k.tj = v & 255;
+      } else {
+        ocm_g8::offdiag_tile(nt, k.offrank, k.ti, k.tj);
       }
+    }
+    const int tile = ocm_g8::tile_index(nt, k.ti, k.tj);
+    const int I = k.ti * Q8T + k.wm * 64, J = k.tj * Q8T + k.wn * 64;
+    int s = 0;
+    while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
+    const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
+    const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
+    Item it;
+    it.nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
+    it.nvs = SKIP ? (int)((r1 - r0 + 63) / 64) : it.nb * SPB;  // stages holding rows (the rest are zero digits)
+    const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
+    const uint32_t span = (uint32_t)((size_t)it.nb * Q8SPB * gstride);
+    const char* cbase = q.digits + gbase * gstride;
+#pragma unroll
+    for (int dg = 0; dg < 3; ++dg) {
+      it.ra[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)I * 32), 0, span, 0x00020000);
+      it.rb[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)J * 32), 0, span, 0x00020000);
+    }
+    it.srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I;
+    it.scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J;
+    float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T) + k.wm * 64 * Q8T + k.wn * 64;
+    it.rout = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, k.dead ? 0u : OUT_SPAN, 0x00020000);
+    return it;
+  };
+
+  i32x4 acc1[4][4], acc2[4][4], acc3[4][4];
+  float SR = 0.f, SC = 0.f;
+  // first: the item's first scale block — the running sums start from +0 instead of being read
+  auto flush = [&](bool first) __attribute__((always_inline)) {
+    constexpr float w2 = 1.f / 254.f, w3 = 1.f / (254.f * 254.f);
+    scl[wave][lane] = SR;  // wave-private: LDS is in order within the wave
+    scl[wave][64 + lane] = SC;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      // row scales of registers 0..3: rows 16a + 4g4 + 0..3
+      const f32x4 si = *reinterpret_cast<const f32x4*>(&scl[wave][a * 16 + 4 * g4]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float sj = scl[wave][64 + c * 16 + l15];
+        f32x4* rp = reinterpret_cast<f32x4*>(&runl[wave][a * 4 + c][lane][0]);
+        f32x4 rv = *rp;
+        if (first) rv = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = fmaf((float)acc3[a][c][e], w3, fmaf((float)acc2[a][c][e], w2, (float)acc1[a][c][e]));
+          rv[e] = fmaf(v, si[e] * sj, rv[e]);
+        }
+        *rp = rv;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // fragment load i (0..23) of a stage, in the order the stage's MFMAs first
+  // use them: A0, B0, B1, B2, B3, A1, A2, A3 (three digits each)
+  auto load_frag = [&](i32x4 (&FA)[4][3], i32x4 (&FB)[4][3], int i, int so, const __amdgpu_buffer_rsrc_t (&da)[3],
+                       const __amdgpu_buffer_rsrc_t (&db)[3]) __attribute__((always_inline)) {
+    const int grp = i / 3, dg = i % 3;
+    if (grp >= 1 && grp <= 4)
+      FB[grp - 1][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(db[dg], voff + (grp - 1) * 512, so, 0);
+    else {
+      const int x = grp == 0 ? 0 : grp - 4;
+      FA[x][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(da[dg], voff + x * 512, so, 0);
+    }
+  };
+  // sub-block i (0..15) of the running sums → the output block behind `ro`
+  auto store_sub = [&](const f32x4& pv, int i, __amdgpu_buffer_rsrc_t ro) __attribute__((always_inline)) {
+    const int a = i >> 2, c = i & 3;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)pv[e]), ro, vout,
+                                            ((a * 16 + e) * Q8T + c * 16) * 4, 0);
+  };
+  // one stage: 96 MFMAs on (CA, CB), sub-blocks row-major, six products each;
+  // the 24 loads at scalar offset `so` behind (da, db) into (NA, NB), one per
+  // four MFMAs.  TAIL (a block's first stage): the previous item's running
+  // sums go out behind `ro`, one sub-block per load slot — read from LDS in
+  // slot i, stored in slot i + 1.
+  auto step = [&](i32x4 (&CA)[4][3], i32x4 (&CB)[4][3], i32x4 (&NA)[4][3], i32x4 (&NB)[4][3], int so,
+                  const __amdgpu_buffer_rsrc_t (&da)[3], const __amdgpu_buffer_rsrc_t (&db)[3], bool z, bool bar,
+                  auto tail, __amdgpu_buffer_rsrc_t ro) __attribute__((always_inline)) {
+    constexpr bool TAIL = decltype(tail)::value;
+    f32x4 pv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 24; ++i) {
+      load_frag(NA, NB, i, so, da, db);
+      if constexpr (TAIL) {
+        if (i >= 1 && i <= 16) store_sub(pv, i - 1, ro);
+        if (i < 16) pv = *reinterpret_cast<const f32x4*>(&runl[wave][i][lane][0]);
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int j = 4 * i + jj, blk = j / 6, kind = j % 6, a = blk >> 2, c = blk & 3;
+        if (kind == 0) acc1[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][0], z ? i32x4{} : acc1[a][c], 0, 0, 0);
+        if (kind == 1) acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][1], z ? i32x4{} : acc2[a][c], 0, 0, 0);
+        if (kind == 2) acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][1], CB[c][0], acc2[a][c], 0, 0, 0);
+        if (kind == 3) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][2], z ? i32x4{} : acc3[a][c], 0, 0, 0);
+        if (kind == 4) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][2], CB[c][0], acc3[a][c], 0, 0, 0);
+        if (kind == 5) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][1], CB[c][1], acc3[a][c], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (bar) __builtin_amdgcn_s_barrier();
+  };
+
+  const __amdgpu_buffer_rsrc_t rnone = __builtin_amdgcn_make_buffer_rsrc((void*)part, 0, 0u, 0x00020000);
+  __amdgpu_buffer_rsrc_t rpend = rnone;  // the output block of the item whose sums are still in runl
+  i32x4 F0A[4][3], F0B[4][3], F1A[4][3], F1B[4][3];
+  Item cur = setup(sl.first);
+#pragma unroll
+  for (int i = 0; i < 24; ++i) load_frag(F0A, F0B, i, 0, cur.ra, cur.rb);
+  for (int n = 0; n < sl.count; ++n) {
+    G8_STAMP(t_in);
+    // the next item (the last item: itself, its prefetch is then a harmless in-range duplicate)
+    const Item nxt = setup(sl.first + min(n + 1, sl.count - 1) * sl.step);
+    if (SKIP && n > 0) {
+#pragma unroll
+      for (int i = 0; i < 24; ++i) load_frag(F0A, F0B, i, 0, cur.ra, cur.rb);
+    }
+#ifdef OCM_G8E_STAMPS
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stage-0 operands are here
+#endif
+    G8_STAMP(t_first);
+    G8_STAMP_VAR(t_last);
+    const int nstage = cur.nb * SPB;
+    for (int blk = 0; blk < cur.nb; ++blk) {
+      const int s0 = blk * SPB;
+      const bool lastb = blk == cur.nb - 1;
+#pragma unroll
+      for (int u = 0; u < SPB; u += 2) {
+        if (SKIP && u > 0 && s0 + u >= cur.nvs) break;
+        if (u == 0) {
+          // (one uniform branch per scale block, between two copies of one
+          // stage: the later blocks' stage 0 carries no dropped stores)
+          if (blk == 0 && n > 0)
+            step(F0A, F0B, F1A, F1B, (s0 + 1) * sstride, cur.ra, cur.rb, true, false, std::true_type{}, rpend);
+          else
+            step(F0A, F0B, F1A, F1B, (s0 + 1) * sstride, cur.ra, cur.rb, true, false, std::false_type{}, rnone);
+          SR = cur.srow[(size_t)blk * q.P8 + lane];
+          SC = cur.scol[(size_t)blk * q.P8 + lane];
+        } else {
+          step(F0A, F0B, F1A, F1B, (s0 + u + 1) * sstride, cur.ra, cur.rb, false, false, std::false_type{}, rnone);
+        }
+        if (!SKIP && u + 2 == SPB) {
+          // the block's last stage loads the next block's stage 0 — or, from
+          // the item's last block, stage 0 of the next item
+          __amdgpu_buffer_rsrc_t da[3], db[3];
+#pragma unroll
+          for (int dg = 0; dg < 3; ++dg) {
+            da[dg] = lastb ? nxt.ra[dg] : cur.ra[dg];
+            db[dg] = lastb ? nxt.rb[dg] : cur.rb[dg];
+          }
+          step(F1A, F1B, F0A, F0B, lastb ? 0 : (s0 + SPB) * sstride, da, db, false, true, std::false_type{}, rnone);
+        } else {
+          step(F1A, F1B, F0A, F0B, min(s0 + u + 2, nstage - 1) * sstride, cur.ra, cur.rb, false, true,
+               std::false_type{}, rnone);
+        }
+      }
+      G8_STAMP_SET(t_last);
+      flush(blk == 0);
+    }
+    rpend = cur.rout;
+    cur = nxt;
+    G8_STAMP(t_out);
+    G8_STAMP_SUM(t_in, t_first, t_last, t_out);
+  }
+  // the last item's sums
+#pragma unroll
+  for (int i = 0; i < 16; ++i) store_sub(*reinterpret_cast<const f32x4*>(&runl[wave][i][lane][0]), i, rpend);
 }
 
 #ifdef OCM_G8_LDS
 // ---------------------------------------------------------------------------
-// k_gram8x (experiment, make exp only: OCM_GRAM8_ORDER=lds) — k_gram8e with
+// k_gram8x (experiment, make exp only: OCM_GRAM8_ORDER=lds) — k_gram8w with
 // the panels shared through LDS.  Measured (r03u, r03v): bit-identical, 362–367
 // TF against the default launch's 439–445 in the same processes, with the
 // partner reads as one burst or split — not kept.  One workgroup per
@@ -2742,18 +2983,22 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   OCM_HIP(hipStreamIsCapturing(st, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  // k_gram8e's block order and wave sync: tile-aligned workgroups with a
+  // The Gram's block order and wave sync: tile-aligned workgroups with a
   // barrier every two stages (437 TF against 417 for the packed walk without
-  // barriers, r03s).  The product library launches only that variant; the
-  // A/B selectors (OCM_GRAM8_ORDER = packed | aligned | sync1 | front | sync4
-  // | sync3, OCM_GRAM8_XCD, OCM_GRAM8_PIECES, OCM_Q8_CG) exist only in
-  // `make exp` builds (OCM_EXP_SELECTORS), which the product never loads.
+  // barriers, r03s), as a persistent kernel (k_gram8e, one workgroup per CU).
+  // The product library launches only that variant; the A/B selectors
+  // (OCM_GRAM8_ORDER = wg | packed | aligned | sync1 | front | sync4 | sync3,
+  // OCM_GRAM8_XCD, OCM_GRAM8_PIECES, OCM_Q8_CG) exist only in `make exp`
+  // builds (OCM_EXP_SELECTORS), which the product never loads.  wg: the same
+  // order with one item per workgroup (k_gram8w), the launch before k_gram8e.
   int order = 3;
-  bool no_remap = false;
+  bool no_remap = false;  // (k_gram8w launches only)
+  (void)no_remap;
   int pieces = 1;
   int qcg = 1;  // column groups per quantiser workgroup
 #ifdef OCM_EXP_SELECTORS
   const char* ord = getenv("OCM_GRAM8_ORDER");
+  if (ord && !strcmp(ord, "wg")) order = 9;
   if (ord && !strcmp(ord, "packed")) order = 0;
   if (ord && !strcmp(ord, "aligned")) order = 1;
   if (ord && !strcmp(ord, "sync1")) order = 2;
@@ -2837,16 +3082,25 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     float* pg = part + (size_t)cprefix[s0] * ntiles * Q8T * Q8T;
     ocm::TimedRegion tr(ctx, OCM_KERNEL_GRAM, st, !unguarded);
 #define G8E_LAUNCH(A_, S_)                                                                                   \
-  hipLaunchKernelGGL((k_gram8e<A_, S_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, \
+  hipLaunchKernelGGL((k_gram8w<A_, S_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, \
                      nwg, nblocks, pg, (no_remap && c0 == 0) ? -1 : (int)c0)
 #define G8E_LAUNCH3(A_, S_, F_)                                                                                      \
-  hipLaunchKernelGGL((k_gram8e<A_, S_, F_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles,         \
+  hipLaunchKernelGGL((k_gram8w<A_, S_, F_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles,         \
                      (int)total, nwg, nblocks, pg, (int)c0)
+    // one workgroup per CU (a CU holds one: ≈ 426 registers per lane); at
+    // least one per XCD, so that every XCD's range of items is served
+    const unsigned pgrid = (unsigned)std::min<int64_t>(total, std::max(ctx->num_cus, ocm_g8::NXCD));
     if (tr_O && !k32 && order == 3)
-      hipLaunchKernelGGL((k_gram8e<true, 2, false, true>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt,
-                         ntiles, (int)total, nwg, nblocks, pg, (int)c0);
-    else if (!k32 && order == 3) G8E_LAUNCH(true, 2);
+      hipLaunchKernelGGL(k_gram8e<true>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
+                         nblocks, pg, (int)c0);
+    else if (!k32 && order == 3)
+      hipLaunchKernelGGL(k_gram8e<false>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
+                         nblocks, pg, (int)c0);
 #ifdef OCM_EXP_SELECTORS
+    else if (tr_O && !k32 && order == 9)
+      hipLaunchKernelGGL((k_gram8w<true, 2, false, true>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt,
+                         ntiles, (int)total, nwg, nblocks, pg, (int)c0);
+    else if (!k32 && order == 9) G8E_LAUNCH(true, 2);
     else if (!k32 && order == 0) G8E_LAUNCH(false, 0);
     else if (!k32 && order == 1) G8E_LAUNCH(true, 0);
     else if (!k32 && order == 2) G8E_LAUNCH(true, 1);
@@ -2884,7 +3138,7 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
       OCM_HIP(hipEventRecord(ev, st));
     }
     for (size_t t = 0; t < tabs.size(); ++t) gram(t, 0, cprefix[tab_s0[t] + tabs[t].nseg] - cprefix[tab_s0[t]]);
-    OCM_CHECK_LAUNCH("k_gram8d/8e");
+    OCM_CHECK_LAUNCH("k_gram8d/8p");
   } else {
     const int64_t gch = cprefix[tab_s0[0] + tabs[0].nseg] - cprefix[tab_s0[0]];
     std::vector<int64_t> cut(pieces + 1);
@@ -2903,6 +3157,18 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     OCM_CHECK_LAUNCH("k_gram8e");
     OCM_HIP(hipStreamWaitEvent(st, ev, 0));  // the read-back is done before the workspace is reused
   }
+#ifdef OCM_G8E_STAMPS  // diagnostic build: the launch's stamp sums to stderr (10 ns units), then cleared
+  {
+    unsigned long long acc[4] = {0, 0, 0, 0};
+    OCM_HIP(hipStreamSynchronize(st));
+    OCM_HIP(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g8_stamp_acc), sizeof(acc)));
+    if (!unguarded && !capturing && acc[3])
+      fprintf(stderr, "G8E_STAMPS order=%d items=%llu mean_us entry_to_first=%.3f last_to_end=%.3f entry_to_end=%.3f\n",
+              order, acc[3], 0.01 * acc[0] / acc[3], 0.01 * acc[1] / acc[3], 0.01 * acc[2] / acc[3]);
+    const unsigned long long zero[4] = {0, 0, 0, 0};
+    OCM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g8_stamp_acc), zero, sizeof(zero)));
+  }
+#endif
   if (tr_O) {
     hipLaunchKernelGGL(k_gram_trace<Q8T>, dim3(Q8T * Q8T / 4 / 256, ntiles), dim3(256), 0, st, part, nt, ntiles, p, 0,
                        cprefix[1], tr_O, tr_part);

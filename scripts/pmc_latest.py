@@ -6,7 +6,9 @@ bench.py reads for its roofline "traffic" field.
     python scripts/pmc_latest.py <pmc dir> <kernel key> <source tag>
 
 Only the launches with the largest grid are averaged (a bench script also
-runs small sample launches).  FETCH_SIZE is doubled: on gfx950 it reports
+runs small sample launches), and of those only the ones within a factor two
+of the counter's largest value: a persistent kernel's grid is the CU count
+whatever the work, so a small sample launch has the same grid.  FETCH_SIZE is doubled: on gfx950 it reports
 half the bytes of wide streaming reads (MI355X_MICROARCH.md §HBM)."""
 import collections
 import csv
@@ -27,8 +29,9 @@ per = collections.defaultdict(list)
 for r in rows:
     if int(r["Grid_Size"]) == gmax:
         per[r["Counter_Name"]].append(float(r["Counter_Value"]))
+per = {n: [x for x in v if x >= 0.5 * max(v)] for n, v in per.items()}
 m = {n: sum(v) / len(v) for n, v in per.items()}
-ent = {"source": tag, "grid_size": gmax, "launches_averaged": max(len(v) for v in per.values()),
+ent = {"source": tag, "grid_size": gmax, "launches_averaged": min(len(v) for v in per.values()),
        "counters_mean_per_launch": m}
 if "FETCH_SIZE" in m:
     ent["fetch_bytes_x2"] = m["FETCH_SIZE"] * 1024 * 2
