@@ -694,6 +694,42 @@ size_t ocm_gemm_bf16_sk_scratch_bytes(int32_t M, int32_t N, int32_t K);
 int ocm_gemm_bf16_sk(ocm_ctx* ctx, int32_t b_nk, const void* A, const void* B, const void* bias, int32_t M, int32_t N,
                      int32_t K, void* C, void* scratch, void* stream);
 
+/* ---- images into objects (appended; the ABI version stays 12) ----
+ * The objects of the data sets come out of an (H, W, p) image (nut_data.py:64-70, 131-144): the band
+ * mean thresholded into a foreground mask, its connected components, and each component's pixel rows.
+ *
+ * ocm_fgmask_f32 / _f64: one read-only pass over the m = H·W pixel rows of X [dev] (any ldx ≥ p, any
+ *   element alignment; 16-byte loads per lane where the base and ldx allow, a scalar tail for p % 4):
+ *   mean_r = (fp64 sum of row r in a fixed order) / p, mask_out[r] = !(mean_r < threshold), the
+ *   reference's ~(mean < thr): a NaN pixel is foreground.  mask_out [dev] m bytes (0 / 1); mean_out
+ *   [dev] m doubles or NULL.  m = 0 is a no-op; OCM_ERR_ARG for m ≥ 2^33.
+ *
+ * ocm_label_u8: connected components of mask [dev] (H × W bytes, non-zero = foreground) with
+ *   connectivity 4 or 8.  labels_out [dev] H × W int32: 0 background, 1..n the components numbered by
+ *   their first pixel in raster order (scipy.ndimage.label's numbering, bit for bit); n_out [dev] one
+ *   int32 = n.  A component's representative is its smallest linear pixel index and its label 1 + the
+ *   rank of that index among the representatives, so the result does not depend on scheduling.
+ *   Union–find in six launches whatever the image holds: tiles labelled in LDS, tile borders united
+ *   with device-scope atomicMin alone (no workgroup waits for another), flatten, and a three-launch
+ *   prefix sum of the representative flags.  No host synchronisation.  Workspace: (H·W + H·W/1024 + 1)
+ *   int32.  OCM_ERR_ARG, before any pointer is looked at, for connectivity other than 4 or 8, H or
+ *   W < 1, or H·W > 2^31 − 1.
+ *
+ * ocm_gather_rows_f32 / _f64: out[i·ldo + j] = X[rows[i]·ldx + j] for i < n, j < p, bit for bit
+ *   (NaN payloads included).  rows [dev] n int64, NOT checked here (as in every entry that takes
+ *   `rows`).  16-byte copies per lane where X, out, ldx, ldo and p allow, element copies otherwise.
+ *   n = 0 is a no-op; OCM_ERR_ARG for n ≥ 2^33. */
+int ocm_fgmask_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, double threshold,
+                   uint8_t* mask_out, double* mean_out, void* stream);
+int ocm_fgmask_f64(ocm_ctx* ctx, const double* X, int64_t ldx, int64_t m, int32_t p, double threshold,
+                   uint8_t* mask_out, double* mean_out, void* stream);
+int ocm_label_u8(ocm_ctx* ctx, const uint8_t* mask, int32_t H, int32_t W, int32_t connectivity, int32_t* labels_out,
+                 int32_t* n_out, void* stream);
+int ocm_gather_rows_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                        float* out, int64_t ldo, void* stream);
+int ocm_gather_rows_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                        double* out, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

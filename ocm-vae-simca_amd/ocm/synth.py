@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["shard_bounds", "spectra_shard", "band_loadings"]
+__all__ = ["shard_bounds", "spectra_shard", "band_loadings", "scene"]
 
 CHUNK = 65536  # rows per generator chunk (the unit of reproducibility)
 
@@ -58,3 +58,42 @@ def spectra_shard(n_total: int, p: int, rank: int, world: int, device, seed: int
         blk = torch.addmm(base.expand(c1 - c0, p), S, L).add_(E, alpha=noise)
         X[a - lo:b - lo] = blk[a - c0:b - c0]
     return X
+
+
+def scene(H: int, W: int, p: int, blobs=8, seed: int = 0, device=None, dtype=torch.float32, offset: float | None = None,
+          return_kinds: bool = False):
+    """An (H, W, p) image in HBM: a background of exact zeros with filled discs
+    whose pixels are ``spectra_shard`` rows + ``offset``; by default the offset
+    is, per kind, the constant that lifts the smallest band mean among the
+    kind's pixels to 1, so every disc pixel stays above a foreground threshold
+    whatever p is (SIMCA centres a constant away).  ``blobs``: a number of discs of kind 0 drawn from ``seed`` (centres
+    anywhere, radii between 1/16 and 1/8 of the shorter side; they may touch or
+    overlap), or a list of (row, col, radius) / (row, col, radius, kind) tuples.
+    Each kind has its own spectral model (its own loadings: the generator seed
+    is a function of ``seed`` and the kind); where discs overlap the later one
+    wins.  With ``return_kinds`` also the (H, W) int64 kind of every pixel, −1
+    for background."""
+    import numpy as np
+
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(blobs, int):
+        rng = np.random.default_rng(seed)
+        lo, hi = max(1, min(H, W) // 16), max(2, min(H, W) // 8)
+        blobs = [(int(rng.integers(0, H)), int(rng.integers(0, W)), int(rng.integers(lo, hi + 1)), 0)
+                 for _ in range(blobs)]
+    yy = torch.arange(H, device=device)[:, None]
+    xx = torch.arange(W, device=device)[None, :]
+    kinds = torch.full((H, W), -1, dtype=torch.int64, device=device)
+    for b in blobs:
+        r, c, rad = b[:3]
+        kinds[(yy - r) ** 2 + (xx - c) ** 2 <= rad * rad] = b[3] if len(b) > 3 else 0
+    cube = torch.zeros((H, W, p), dtype=dtype, device=device)
+    flat, kflat = cube.view(H * W, p), kinds.view(-1)
+    for kind in sorted({int(b[3]) if len(b) > 3 else 0 for b in blobs}):
+        idx = torch.nonzero(kflat == kind).view(-1)
+        if idx.numel():
+            rows = spectra_shard(idx.numel(), p, 0, 1, device, seed=seed + 7919 * (kind + 1))
+            shift = offset if offset is not None else (1.0 - rows.double().mean(dim=1).min()).clamp(min=0.0)
+            flat[idx] = (rows.double() + shift).to(dtype)
+    return (cube, kinds) if return_kinds else cube
