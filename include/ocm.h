@@ -730,6 +730,40 @@ int ocm_gather_rows_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t
 int ocm_gather_rows_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
                         double* out, int64_t ldo, void* stream);
 
+/* ---- PLS-DA (appended; the ABI version stays 12) ----
+ * The discriminant baseline of data_cheese.py:193-328: PLSRegression(a) on the class target, then
+ * LinearDiscriminantAnalysis on the PLS scores, for every a and every cross-validation fold.
+ *
+ * ocm_pls_fit_f64: the PLS recursion of `nprob` independent problems (the full fit and every fold) on
+ *   their moments.  S [dev] nprob × p × p = XcᵀXc and s [dev] nprob × p × M = XcᵀYc of the centred,
+ *   scaled training rows (neither is changed); 1 ≤ M ≤ 8, 1 ≤ A ≤ min(p, 64).  For a = 0..A−1:
+ *   w = s (M = 1) or s·c with c the dominant eigenvector of sᵀs (cyclic Jacobi, fp64), scaled to unit
+ *   norm with its largest-magnitude entry positive (sklearn's _svd_flip_1d);
+ *   r = w − Σ_{j<a} (p_jᵀw) r_j;  v = S r;  tt = rᵀv;  p_a = v / tt;  q_a = sᵀr / tt;  s −= tt p_a q_aᵀ.
+ *   W_out, R_out, P_out [dev] nprob × A × p; q_out [dev] nprob × A × M; tt_out [dev] nprob × A;
+ *   ncomp_out [dev] nprob int32, the components completed: a problem stops at the first step where
+ *   ‖s‖² ≤ 2⁻¹⁰⁰ ‖s₀‖² or tt ≤ 0 (sklearn's "y residual is constant") and its later rows are zeros.
+ *   Two launches per component whatever nprob is, no workgroup waits for another, every sum in a fixed
+ *   order (two calls give the same bits).  Workspace: nprob · (p · (3 + M) + 8) doubles, whatever A is.
+ *
+ * ocm_plsda_predict_f32: t = P (x − mu) for the m processed rows in one read of X (any p ≥ 1, any
+ *   ldx ≥ p, optional `rows`), P [dev] k × p doubles, mu [dev] p doubles, 1 ≤ k ≤ 64: f32 MFMA
+ *   products, f32 chains over 256 columns added up in fp64.  Then, for each of the nlv prefixes lvs[l]
+ *   ([host] int32, ascending, 1 ≤ lvs[l] ≤ k, 0 ≤ nlv ≤ 64) and each class c < C (2 ≤ C ≤ 8),
+ *   D[l][c] = Σ_{a<lvs[l]} coef[l][c][a] t_a + b[l][c] in fp64 and pred[l] = the lowest c at the maximum
+ *   (np.argmax).  table [dev]: nlv × C × k coefficients, then nlv × C intercepts.  Outputs, each
+ *   nullable: T_out [dev] m × k float32; D_out [dev] m × nlv × C float32; pred_out [dev] m × nlv
+ *   uint8; counts_out [dev] nlv × C × C int64, counts[l][true][pred] over the rows whose y_true
+ *   ([dev] m uint8 class indices) is < C (other rows count nowhere); counts_out needs y_true.
+ *   nlv = 0 gives the scores alone.  m = 0 writes zero counts. */
+int ocm_pls_fit_f64(ocm_ctx* ctx, const double* S, const double* s, int32_t nprob, int32_t p, int32_t M, int32_t A,
+                    double* W_out, double* R_out, double* P_out, double* q_out, double* tt_out, int32_t* ncomp_out,
+                    void* stream);
+int ocm_plsda_predict_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                          const double* P, const double* mu, int32_t k, const int32_t* lvs, int32_t nlv, int32_t C,
+                          const double* table, float* T_out, float* D_out, uint8_t* pred_out, const uint8_t* y_true,
+                          int64_t* counts_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -449,6 +449,65 @@ def segment_sums(X, offsets, checked: bool = False) -> torch.Tensor:
     return out
 
 
+def pls_fit(S: torch.Tensor, s: torch.Tensor, A: int) -> dict:
+    """The PLS recursion of nprob problems on their moments (ocm_pls_fit_f64):
+    S (nprob, p, p) = XcᵀXc and s (nprob, p, M) = XcᵀYc, float64 device tensors.
+    Returns device tensors ``W``, ``R``, ``P`` (nprob, A, p), ``q`` (nprob, A, M),
+    ``tt`` (nprob, A) and ``ncomp`` (nprob,) int32; rows past a problem's
+    ``ncomp`` are zeros."""
+    if not (S.is_cuda and S.dtype == torch.float64 and s.dtype == torch.float64 and S.dim() == 3 and s.dim() == 3):
+        raise ValueError("pls_fit: S (nprob, p, p) and s (nprob, p, M) must be float64 device tensors")
+    nprob, p, M = s.shape
+    if S.shape != (nprob, p, p):
+        raise ValueError("pls_fit: S must be (nprob, p, p) for s (nprob, p, M)")
+    S, s = S.contiguous(), s.contiguous()
+    dev = S.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"W": torch.empty((nprob, A, p), **f64), "R": torch.empty((nprob, A, p), **f64),
+           "P": torch.empty((nprob, A, p), **f64), "q": torch.empty((nprob, A, M), **f64),
+           "tt": torch.empty((nprob, A), **f64), "ncomp": torch.empty(nprob, dtype=torch.int32, device=dev)}
+    check(_lib.load().ocm_pls_fit_f64(Context.get(dev.index).handle, ptr(S), ptr(s), nprob, p, M, int(A),
+                                      ptr(out["W"]), ptr(out["R"]), ptr(out["P"]), ptr(out["q"]), ptr(out["tt"]),
+                                      ptr(out["ncomp"]), _stream(dev)), "ocm_pls_fit_f64")
+    return out
+
+
+def plsda_predict(X: torch.Tensor, rows: torch.Tensor | None, m: int, P64: torch.Tensor, mean64: torch.Tensor,
+                  lvs=(), C: int = 0, table: torch.Tensor | None = None, want_T=False, want_D=False, want_pred=True,
+                  y_true: torch.Tensor | None = None, outs: dict | None = None) -> dict:
+    """Projection and LDA sweep in one read of X (ocm_plsda_predict_f32):
+    t = P64 (x − mean64) with P64 (k, p) float64, then for every prefix length in
+    ``lvs`` (ascending) the C class scores D = coef·t[:lv] + b from ``table``
+    (nlv·C·k coefficients then nlv·C intercepts, float64, device), the first
+    class at the maximum, and with ``y_true`` (m uint8 class indices, device) the
+    confusion counts (nlv, C, C) int64.  X: float32 device matrix, row stride
+    ≥ p.  Returns the device tensors ``T`` (m, k) f32, ``D`` (m, nlv, C) f32,
+    ``pred`` (m, nlv) uint8, ``counts``; ``outs`` may supply them."""
+    k, p = P64.shape
+    dev = X.device
+    if X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != p or (p > 1 and X.stride(1) != 1):
+        raise ValueError("plsda_predict: X must be a float32 device matrix of p unit-stride columns")
+    lv = [int(v) for v in lvs]
+    nlv = len(lv)
+    outs = dict(outs or {})
+    T = outs.get("T", torch.empty((m, k), dtype=torch.float32, device=dev) if want_T else None)
+    D = outs.get("D", torch.empty((m, nlv, C), dtype=torch.float32, device=dev) if want_D and nlv else None)
+    pred = outs.get("pred", torch.empty((m, nlv), dtype=torch.uint8, device=dev) if want_pred and nlv else None)
+    counts = outs.get("counts", torch.empty((nlv, C, C), dtype=torch.int64, device=dev)
+                      if y_true is not None and nlv else None)
+    if y_true is not None and (y_true.dtype != torch.uint8 or y_true.numel() != m or not y_true.is_contiguous()):
+        raise ValueError("plsda_predict: y_true must be a contiguous uint8 tensor of m class indices")
+    if nlv and (table is None or table.dtype != torch.float64 or table.numel() != nlv * C * (k + 1)):
+        raise ValueError("plsda_predict: table must hold nlv·C·k coefficients and nlv·C intercepts (float64)")
+    arr = (ctypes.c_int32 * max(nlv, 1))(*lv)
+    ldx = X.stride(0) if X.shape[0] > 1 else p
+    check(_lib.load().ocm_plsda_predict_f32(Context.get(dev.index).handle, ptr(X), ldx, ptr(rows), m, p,
+                                            ptr(P64.contiguous()), ptr(mean64), k, arr, nlv, int(C),
+                                            ptr(table.contiguous()) if nlv else None, ptr(T), ptr(D), ptr(pred),
+                                            ptr(y_true), ptr(counts), _stream(dev)), "ocm_plsda_predict_f32")
+    return {"T": T, "D": D, "pred": pred, "counts": counts}
+
+
 def confusion_counts(accept: torch.Tensor, positive: torch.Tensor, stride: int = 1) -> torch.Tensor:
     """{TP, TN, FP, FN} (int64, device) of a 0/1 prediction column ``accept``
     (float64, read at ``stride``) against the uint8 mask ``positive``."""
