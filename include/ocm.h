@@ -310,6 +310,26 @@ int ocm_cv_counts(ocm_ctx* ctx, const float* T, int64_t m, int32_t k, const floa
                   const uint8_t* positive, int64_t m_split, const ocm_cv_config* cfg, int32_t ncfg,
                   uint64_t* counts_out, double* accept_out, void* stream);
 
+/* Per-object votes and decision sums of every configuration over rows scored
+ * at LV_max (object-wise cross-validation; the object rules of
+ * SIMCA.predict_objects, utils/SIMCA.py:560-564).  T, Q, inv_evals and cfg
+ * [host] as for ocm_cv_counts.  Objects are runs of adjacent rows: offsets
+ * [dev] G + 1 non-decreasing int64 with offsets[0] = 0 and offsets[G] = m (not
+ * checked here: offsets that break this give wrong results, never an access
+ * out of bounds).  Outputs [dev], either nullable but not both:
+ *   votes_out ncfg×G uint32: the rows of object g that configuration c
+ *     accepts, the accept being that of ocm_cv_counts bit for bit;
+ *   dsum_out  ncfg×G doubles: Σ over the rows of object g of dlim_c − d_red,c(row)
+ *     (decision_function), summed in an order fixed by m, the offsets and ncfg
+ *     alone, without atomics: the same bits on every call, with or without
+ *     votes_out.
+ * An object without rows gets 0.  k ≤ 64, ncfg ≤ OCM_CV_MAXCFG; m = 0 or G = 0
+ * is a successful no-op.  Per-chunk partial sums use the context workspace
+ * (24 bytes per 256 rows and configuration). */
+int ocm_cv_objects(ocm_ctx* ctx, const float* T, int64_t m, int32_t k, const float* Q, const double* inv_evals,
+                   const int64_t* offsets, int64_t G, const ocm_cv_config* cfg, int32_t ncfg,
+                   uint32_t* votes_out, double* dsum_out, void* stream);
+
 /* Confusion counts of one class column of a prediction matrix
  * (utils/SIMCA.py:238-245, called from predict(X, y_true) at :146-152):
  * accept [dev] m doubles 0/1 at stride accept_stride (the column written by

@@ -1,7 +1,9 @@
 """Fold engine for class-wise SIMCA cross-validation (C3).
 
 Replaces the per-(combo, LV, fold) refit loop of utils/CVSIMCA.py:145-222
-for this package's SIMCA under a ``ClasswiseKFoldWithExternalVal`` split:
+for this package's SIMCA under a ``ClasswiseKFoldWithExternalVal`` split, or
+under an ``ocm.objectcv.ObjectKFoldWithExternalVal`` split (folds of whole
+objects, taken from the splitter; single process):
 
 * one segmented Gram pass over the target-class rows, segments = folds
   (``ocm_gram_f32``); fold f trains on Gram(total) − Gram(f) (fp64
@@ -16,6 +18,10 @@ for this package's SIMCA under a ``ClasswiseKFoldWithExternalVal`` split:
   counts for every (param combo, LV) decision at once;
 * training-row statistics (``perc`` / ``chi2pom`` limits) come from one more
   scoring of the fold's training rows and ``ocm_cv_prefix``.
+
+* on request (``objects=``, ocm/objectcv.py) the same scores are reduced to
+  per-object votes and decision sums for every configuration
+  (``ocm_cv_objects``), for CV records that count objects.
 
 Aggregation is the reference's: spec = mean over folds of TN/(TN+FP)·100
 (:195-203), sens from the pooled prediction vector, where target rows carry
@@ -72,13 +78,16 @@ class _Spec:
 
 def _applicable(base_est, X, y, cv, lv_values, param_grid):
     """The fold engine covers this package's SIMCA (not wrapped in a Pipeline),
-    a ClasswiseKFoldWithExternalVal split, an LV sweep, and a single target
-    label whose model_class is that label (or None)."""
+    a ClasswiseKFoldWithExternalVal or ObjectKFoldWithExternalVal split, an LV
+    sweep, and a single target label whose model_class is that label (or None)."""
     from sklearn.model_selection import ParameterGrid
     from utils.CVSIMCA import ClasswiseKFoldWithExternalVal
     from utils.SIMCA import SIMCA
 
-    if type(base_est) is not SIMCA or not isinstance(cv, ClasswiseKFoldWithExternalVal):
+    from .objectcv import ObjectKFoldWithExternalVal
+
+    if type(base_est) is not SIMCA or not isinstance(cv, (ClasswiseKFoldWithExternalVal,
+                                                          ObjectKFoldWithExternalVal)):
         return None
     if lv_values is None or len(lv_values) == 0 or y is None:
         return None
@@ -109,6 +118,17 @@ def _applicable(base_est, X, y, cv, lv_values, param_grid):
 def grid(base_est, X, y, cv, lv_values, param_grid, class_index, store_predictions):
     """utils/CVSIMCA.py drop-in hook: (records, by_combo), or (None, None)
     when the fold engine does not cover the configuration."""
+    from .objectcv import ObjectKFoldWithExternalVal
+
+    if isinstance(cv, ObjectKFoldWithExternalVal):
+        # object-wise folds are per-process: the single-process engine on the rows
+        # given, no fingerprint exchange and no collective (as predict_objects)
+        app = _applicable(base_est, X, y, cv, lv_values, param_grid)
+        if app is None:
+            return None, None
+        cls_idx, tl, combos, base = app
+        return cv_grid(X, np.asarray(y), cv.target_folds(X, y), cls_idx, lv_values, combos, base,
+                       [tl] if class_index is None else class_index, store_predictions)
     try:
         app, err = _applicable(base_est, X, y, cv, lv_values, param_grid), None
     except Exception as e:  # raised after the exchange, so the other ranks are not left waiting in it
@@ -182,10 +202,18 @@ def _rates(TP, TN, FP, FN):
 
 
 def cv_grid(X, y, folds, cls_idx, lv_values, combos, base_params, class_index, store_predictions,
-            row_offset=0, group=None):
+            row_offset=0, group=None, objects=None):
     """The fold engine.  X: this rank's rows (host array or device tensor) =
     global rows [row_offset, row_offset + len(X)); y, folds, cls_idx: global.
-    Returns (records, by_combo) in the reference's record order."""
+    Returns (records, by_combo) in the reference's record order.
+
+    ``objects`` (an ``ocm.objectcv.ObjectTables``, single process only): every
+    fold's test rows are also reduced to per-object votes and decision sums
+    for all configurations (``ocm_cv_objects`` on the scores ``ocm_cv_counts``
+    reads) and handed to ``objects.add_fold``; the folds must be unions of
+    whole objects."""
+    if objects is not None and (group is not None or row_offset != 0):
+        raise ValueError("cv_grid: the object tables are per-process (no group, row_offset = 0)")
     Xd = engine.as_device_f32(X)
     dev = Xd.device
     n_loc, p = Xd.shape
@@ -384,6 +412,13 @@ def cv_grid(X, y, folds, cls_idx, lv_values, combos, base_params, class_index, s
             sc = engine.score(Xd, rows, m, evecs, mean, inv, want_T=True, want_T2=False, want_Q=True)
             cnt, acc = engine.cv_counts(sc["T"], sc["Q"], inv, pos, int(fold_loc.size), configs,
                                         want_accept=store_predictions)
+            if objects is not None:
+                # fold rows then other rows, each ascending: the test objects are runs
+                off_t, obj_t = objects.test_runs(test_loc, int(fold_loc.size))
+                votes, dsum = engine.cv_objects(sc["T"], sc["Q"], inv, off_t, configs,
+                                                want_votes=objects.want_votes, want_dsum=objects.want_dsum,
+                                                checked=True)
+                objects.add_fold(f, obj_t, off_t, votes, dsum)
             del sc
         else:
             cnt = torch.zeros((ncfg, 2, 4), dtype=torch.int64, device=dev)

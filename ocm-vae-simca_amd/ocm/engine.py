@@ -581,6 +581,52 @@ def cv_counts(T: torch.Tensor, Q: torch.Tensor, inv_evals: torch.Tensor, positiv
     return counts, acc
 
 
+def cv_objects(T: torch.Tensor, Q: torch.Tensor, inv_evals: torch.Tensor, offsets, configs, want_votes=True,
+               want_dsum=True, checked: bool = False):
+    """Per-object votes (ncfg, G) int64 and decision sums (ncfg, G) float64 of
+    rows scored at LV_max (ocm_cv_objects): votes[c, g] rows of object g accepted
+    by configuration c (``cv_counts``' accept), dsum[c, g] = Σ dlim_c − d_red,c
+    over them, the same bits on every call.  ``offsets``: G + 1 row offsets from
+    0 to m with no empty object, host array-like or an int64 device tensor,
+    validated on the host unless ``checked=True``; configs as for ``cv_counts``.
+    Returns (votes, dsum); an output not asked for is None."""
+    from .objects import check_offsets
+
+    m, k = T.shape
+    dev = T.device
+    if not (want_votes or want_dsum):
+        raise ValueError("cv_objects: ask for votes, dsum or both")
+    on_dev = isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.dtype == torch.int64
+    if not checked:
+        off_h = check_offsets(offsets, m)
+        if off_h[0] != 0 or off_h[-1] != m:
+            raise ValueError(f"cv_objects: offsets must run from 0 to {m}, got {int(off_h[0])} to {int(off_h[-1])}")
+        if (np.diff(off_h) == 0).any():
+            raise ValueError(f"cv_objects: object {int(np.flatnonzero(np.diff(off_h) == 0)[0])} is empty")
+        off = offsets.to(dev).contiguous() if on_dev else torch.from_numpy(off_h).to(dev)
+    else:
+        off = offsets.to(dev).contiguous() if on_dev else \
+            torch.from_numpy(np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))).to(dev)
+    if off.dim() != 1 or off.numel() < 1:
+        raise ValueError("cv_objects: offsets must be a 1-D tensor of G + 1 >= 1 row offsets")
+    G = off.numel() - 1
+    nc = len(configs)
+    votes = torch.empty((nc, G), dtype=torch.int32, device=dev) if want_votes else None
+    dsum = torch.empty((nc, G), dtype=torch.float64, device=dev) if want_dsum else None
+    T, Q = T.contiguous(), Q.contiguous()
+    for c0 in range(0, nc, _lib.OCM_CV_MAXCFG):
+        part = configs[c0:c0 + _lib.OCM_CV_MAXCFG]
+        n = len(part)
+        arr = (_lib.OcmCvConfig * n)(*[_lib.OcmCvConfig(int(lv), TYPE_CODES[ty], float(a), float(b), float(d))
+                                       for (lv, ty, a, b, d) in part])
+        check(_lib.load().ocm_cv_objects(Context.get(dev.index).handle, ptr(T), m, k, ptr(Q), ptr(inv_evals),
+                                         ptr(off), G, arr, n, ptr(votes[c0:] if votes is not None else None),
+                                         ptr(dsum[c0:] if dsum is not None else None), _stream(dev)),
+              "ocm_cv_objects")
+    # uint32 counts of at most m < 2^31 rows each: the int32 view holds them; int64 for the arithmetic on them
+    return (votes.to(torch.int64) if votes is not None else None), dsum
+
+
 def radix_hist(v: torch.Tensor, prefix: int, shift: int, hist: torch.Tensor | None = None) -> torch.Tensor:
     """One radix-select pass (ocm_radix_hist): 256-bin counts of the order keys
     of ``v`` that match ``prefix`` above bit ``shift + 8``, binned by the 8 bits

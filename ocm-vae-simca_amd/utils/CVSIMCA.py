@@ -17,7 +17,8 @@ Contract (reference file:line):
 * ``plot_cv`` (:274-331): the CV metric against LV for one parameter set.
 
 Execution: when the estimator is this package's SIMCA under a
-``ClasswiseKFoldWithExternalVal`` split, ``ocm.cv`` evaluates the whole grid
+``ClasswiseKFoldWithExternalVal`` split (or the object-wise
+``ocm.objectcv.ObjectKFoldWithExternalVal``), ``ocm.cv`` evaluates the whole grid
 on the GPU in one Gram pass (fold Grams by downdating, one eigensolve per
 fold, every LV a prefix of it).  Anything else (pipelines, other splitters,
 foreign estimators) goes through ``_crossval_loop``: per setting, a clone is
