@@ -784,6 +784,40 @@ int ocm_plsda_predict_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64
                           const double* table, float* T_out, float* D_out, uint8_t* pred_out, const uint8_t* y_true,
                           int64_t* counts_out, void* stream);
 
+/* ---- multi-class SIMCA (appended; the ABI version stays 12) ----
+ * The reference's SIMCA is a multi-class estimator (model_class=None fits every class,
+ * utils/SIMCA.py:27-59) whose predict loops over the classes and reads X once per class
+ * (utils/SIMCA.py:120-145); data_cheese.py:193-328 reads its one-class results against PLS-DA on the
+ * same rows.  ocm_score_multi_f32 scores the m processed rows (all rows, or X[rows[r]]) against C class
+ * models in one launch and ends in the class assignment.
+ *   koff [host] C + 1 ascending offsets, koff[0] = 0: class c owns the stacked components
+ *     koff[c] .. koff[c+1] − 1; K = koff[C].  1 ≤ C ≤ 8, every k_c in [1, p], K ≤ 64 (else OCM_ERR_ARG).
+ *   P [dev] K × p float64, each class's rows orthonormal; mu [dev] C × p float64; a_diag [dev] K float64
+ *     (1/λ); dec [host] C ocm_decision, one per class.  Any p ≥ 1, any ldx ≥ p, no alignment requirement.
+ * Per processed row and class c, with y = x − μ_c and t = P_c·y:
+ *   Q_c = ‖y − P_cᵀt‖² (the explicit residual, f32), T²_c = Σ t²·a (fp64), dred_c as ocm_decide forms it
+ *   from T²_c and the float32 Q_c, accept_c = dred_c < dlim_c, ratio_c = dred_c / dlim_c (fp64).
+ *   naccept = the number of accepting classes; nearest = the lowest c at the smallest ratio_c over all
+ *   classes (a NaN ratio counts as +inf; all NaN: 0); index = the lowest accepting c at the smallest
+ *   ratio_c among the accepting classes, −1 when none accepts.
+ * Outputs [dev], every one nullable: T2_out m × C float64, Q_out m × C float32, ratio_out m × C float64,
+ *   accept_out[r·accept_stride + c] = 1.0 / 0.0 (accept_stride ≥ C: predict's matrix), index_out m int8,
+ *   nearest_out and naccept_out m uint8, counts_out (C + 1)·(3C + 2) int64, which needs y_true [dev]
+ *   (m uint8 class indices; a value ≥ C is the row "other" = C) and holds three blocks in this order:
+ *   table[C+1][C+1] ([true][index, column C = none]), acc[C+1][C] ([true][class] accepted) and
+ *   hist[C+1][C+1] ([true][naccept]).  m = 0 writes zero counts.
+ * Numerics: f32 MFMA products; t in f32 chains over 64 columns flushed to fp64; the mean as a float pair
+ *   (hi + lo); the residual in f32; T², dred and ratio in fp64.  The counts are integer sums (64-bit
+ *   integer atomics, no floating-point atomics): two launches on one input give the same bytes in every
+ *   output.  X is read from HBM once for all classes where a 16-row tile fits half a CU's LDS beside the
+ *   kernel's static arrays (p ≤ ≈ 1100); for wider rows the later sweeps read the tile again through the
+ *   cache hierarchy.  Workspace: (K + 2C)·p floats. */
+int ocm_score_multi_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                        const double* P, const double* mu, const double* a_diag, const int32_t* koff, int32_t C,
+                        const ocm_decision* dec, double* T2_out, float* Q_out, double* ratio_out,
+                        double* accept_out, int64_t accept_stride, int8_t* index_out, uint8_t* nearest_out,
+                        uint8_t* naccept_out, const uint8_t* y_true, int64_t* counts_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

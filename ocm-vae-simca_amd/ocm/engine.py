@@ -508,6 +508,75 @@ def plsda_predict(X: torch.Tensor, rows: torch.Tensor | None, m: int, P64: torch
     return {"T": T, "D": D, "pred": pred, "counts": counts}
 
 
+MULTI_WANT = ("T2", "Q", "ratio", "pred", "index", "nearest", "n_accept")
+MULTI_MAXC, MULTI_MAXK = 8, 64  # ocm_score_multi_f32's limits (include/ocm.h)
+
+
+def stack_models(fits) -> dict:
+    """The operands of ``score_multi`` for a list of ``ClassFit``: ``P`` (K, p),
+    ``mu`` (C, p) and ``a`` (K,) float64 device tensors stacked in class order,
+    ``koff`` the C + 1 component offsets and ``ks`` the components per class."""
+    ks = [int(f.P64.shape[0]) for f in fits]
+    return {"P": torch.cat([f.P64 for f in fits]).contiguous(),
+            "mu": torch.stack([f.mean64 for f in fits]).contiguous(),
+            "a": torch.cat([f.inv_diag for f in fits]).contiguous(),
+            "koff": [0] + [int(v) for v in np.cumsum(ks)], "ks": ks}
+
+
+def score_multi(X: torch.Tensor, rows: torch.Tensor | None, m: int, fits, decisions, want=MULTI_WANT,
+                y_true: torch.Tensor | None = None, stack: dict | None = None) -> dict:
+    """All class models against the processed rows in one launch
+    (ocm_score_multi_f32): per class T², Q, ``ratio`` = dred / D_limit and the
+    0/1 ``pred`` matrix, then ``index`` (the accepting class at the smallest
+    ratio, −1: none), ``nearest`` and ``n_accept`` per row, and with ``y_true``
+    (m uint8 class indices, device; ≥ C: "other") the three count blocks
+    ``table`` (C + 1, C + 1), ``accept_counts`` (C + 1, C) and ``n_accept_hist``
+    (C + 1, C + 1), int64.  ``fits``: the ``ClassFit`` of each class (or
+    ``stack`` = ``stack_models(fits)``, built once and reused); ``decisions``:
+    one ``OcmDecision`` per class; ``want``: the per-row outputs to write.
+    X: a float32 device matrix with row stride ≥ p; at most 8 classes and 64
+    components in all (ValueError beyond).  Returns device tensors (``index``
+    int8, ``nearest`` / ``n_accept`` uint8; None where not wanted)."""
+    st = stack if stack is not None else stack_models(fits)
+    K, p = st["P"].shape
+    C = len(st["ks"])
+    dev = X.device
+    if X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != p or (p > 1 and X.stride(1) != 1):
+        raise ValueError("score_multi: X must be a float32 device matrix of p unit-stride columns")
+    if len(decisions) != C:
+        raise ValueError(f"score_multi: {len(decisions)} decisions for {C} classes")
+    if y_true is not None and (y_true.dtype != torch.uint8 or y_true.numel() != m or not y_true.is_contiguous()):
+        raise ValueError("score_multi: y_true must be a contiguous uint8 tensor of m class indices")
+    unknown = set(want) - set(MULTI_WANT)
+    if unknown:
+        raise ValueError(f"score_multi: unknown outputs {sorted(unknown)}")
+
+    def alloc(name, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev) if name in want else None
+
+    out = {"T2": alloc("T2", (m, C), torch.float64), "Q": alloc("Q", (m, C), torch.float32),
+           "ratio": alloc("ratio", (m, C), torch.float64), "pred": alloc("pred", (m, C), torch.float64),
+           "index": alloc("index", (m,), torch.int8), "nearest": alloc("nearest", (m,), torch.uint8),
+           "n_accept": alloc("n_accept", (m,), torch.uint8)}
+    counts = torch.empty((C + 1) * (3 * C + 2), dtype=torch.int64, device=dev) if y_true is not None else None
+    koff = (ctypes.c_int32 * (C + 1))(*st["koff"])
+    dec = (OcmDecision * C)(*decisions)
+    ldx = X.stride(0) if X.shape[0] > 1 else p
+    check(_lib.load().ocm_score_multi_f32(Context.get(dev.index).handle, ptr(X), ldx, ptr(rows), m, p, ptr(st["P"]),
+                                          ptr(st["mu"]), ptr(st["a"]), koff, C, dec, ptr(out["T2"]), ptr(out["Q"]),
+                                          ptr(out["ratio"]), ptr(out["pred"]), C, ptr(out["index"]),
+                                          ptr(out["nearest"]), ptr(out["n_accept"]), ptr(y_true), ptr(counts),
+                                          _stream(dev)), "ocm_score_multi_f32")
+    if counts is not None:
+        C1 = C + 1
+        out["table"] = counts[:C1 * C1].view(C1, C1)
+        out["accept_counts"] = counts[C1 * C1:C1 * C1 + C1 * C].view(C1, C)
+        out["n_accept_hist"] = counts[C1 * C1 + C1 * C:].view(C1, C1)
+    else:
+        out["table"] = out["accept_counts"] = out["n_accept_hist"] = None
+    return out
+
+
 def confusion_counts(accept: torch.Tensor, positive: torch.Tensor, stride: int = 1) -> torch.Tensor:
     """{TP, TN, FP, FN} (int64, device) of a 0/1 prediction column ``accept``
     (float64, read at ``stride``) against the uint8 mask ``positive``."""

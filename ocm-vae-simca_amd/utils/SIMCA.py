@@ -61,11 +61,12 @@ from sklearn.base import BaseEstimator, ClassifierMixin
 
 from ocm import engine, limits
 from ocm.dist import make_allreduce
+from ocm.multiclass import ClassifyResult
 from ocm.prepview import PrepView
 from ocm.replica import gather_rows, replicated_group
 from ocm.synth import shard_bounds
 
-__all__ = ["SIMCA", "ContributionResult", "ObjectResult"]
+__all__ = ["SIMCA", "ContributionResult", "ObjectResult", "ClassifyResult"]
 
 
 @dataclass
@@ -493,6 +494,128 @@ class SIMCA(BaseEstimator, ClassifierMixin):
                 if v is not None:
                     setattr(out, name, _np(v))
         return out
+
+    # -------------------------------------------------- multi-class decisions
+    def _classify_check(self, X, y_true, who):
+        """The argument checks of ``classify`` / ``model_distance`` (no device work)."""
+        from sklearn.exceptions import NotFittedError
+
+        if not getattr(self, "_fits", None):
+            raise NotFittedError(f"{who}: this SIMCA instance is not fitted yet; call fit first")
+        classes = list(self.model_class)
+        if len(classes) > 255:
+            raise ValueError(f"{who}: {len(classes)} classes (at most 255: class indices are bytes)")
+        if len(X.shape) != 2 or int(X.shape[1]) != int(self.n_features_in_):
+            raise ValueError(f"{who}: X has shape {tuple(X.shape)}, the model was fitted on "
+                             f"{int(self.n_features_in_)} columns")
+        m = int(X.shape[0])
+        yi = None
+        if y_true is not None:
+            yt = _host_labels(y_true)
+            if yt.shape != (m,):
+                raise ValueError(f"{who}: y_true has shape {yt.shape}, X has {m} rows")
+            yi = np.full(m, len(classes), dtype=np.uint8)  # rows of no modelled class: "other" = C
+            for i, cls in enumerate(classes):
+                yi[yt == cls] = i
+        return classes, m, yi
+
+    def classify(self, X, y_true=None, distances=False, none_label=-1, route=None):
+        """Every row of X against all class models at once (the reference's
+        ``predict`` loop, utils/SIMCA.py:120-145, read as a classifier; what
+        data_cheese.py:193-328 compares with PLS-DA): a ``ClassifyResult`` with
+        ``predict``'s 0/1 matrix, ``ratio = dred / D_limit`` per class, the
+        assigned class ``index`` / ``label`` (the accepting class at the smallest
+        ratio; −1 / ``none_label`` when no class accepts), the ``nearest`` class,
+        ``n_accept``, with ``distances=True`` the (m, C) ``T2`` and ``Q``, and with
+        ``y_true`` the count tables (rows of no modelled class in row C) and the
+        per-class ``metrics`` that ``predict(X, y_true)`` stores in
+        ``self.metrics``.  The decisions are ``predict``'s (the ``dd`` last-class
+        quirk included).
+
+        float32 spectra of a model with at most 8 classes and 64 components in
+        all take one launch for all classes (ocm_score_multi_f32) on the shapes
+        where it is the faster route (``ocm.multiclass.fused_is_faster``); other
+        shapes, float64 spectra, a lazy view and larger models take the
+        per-class kernels (``ocm.multiclass.classify_composed``).  ``route``
+        ("fused" / "composed") forces one of the two, for tests and timings.
+
+        NumPy in, NumPy out; tensor or lazy view in, device tensors out.  Sets
+        no state on the estimator and prints nothing.  A model fitted
+        row-sharded under torchrun holds the full model on every rank:
+        ``classify`` scores all its rows on the calling rank, with no collective
+        and no fingerprint exchange."""
+        from ocm import multiclass as _mc
+
+        classes, m, yi = self._classify_check(X, y_true, "classify")
+        if route not in (None, "fused", "composed"):
+            raise ValueError(f"classify: route={route!r} (None, 'fused' or 'composed')")
+        C = len(classes)
+        fits = [self._fits[cls] for cls in classes]
+        decs = []
+        for cls in classes:
+            info = self._model[cls]
+            decs.append(self._decision(info["T2_limit"], info["Q_limit"], info["D_limit"]))
+        Xd = engine._plain(engine.as_device_x(X))
+        dev = Xd.device
+        ks = [int(f.k) for f in fits]
+        takes = (isinstance(Xd, torch.Tensor) and Xd.dtype == torch.float32 and C <= engine.MULTI_MAXC and
+                 sum(ks) <= engine.MULTI_MAXK)
+        if route == "fused" and not takes:
+            raise ValueError("classify: route='fused' takes float32 spectra, at most 8 classes and 64 components")
+        fused = takes and (route == "fused" or (route is None and _mc.fused_is_faster(int(Xd.shape[1]), ks)))
+        ydev = torch.from_numpy(yi).to(dev) if yi is not None else None
+        if fused:
+            key = tuple(id(f) for f in fits)
+            cached = self.__dict__.get("_multi_stack")
+            if cached is None or cached[0] != key:
+                cached = self.__dict__["_multi_stack"] = (key, engine.stack_models(fits))
+            want = engine.MULTI_WANT if distances else tuple(w for w in engine.MULTI_WANT if w not in ("T2", "Q"))
+            out = engine.score_multi(Xd, None, m, fits, decs, want=want, y_true=ydev, stack=cached[1])
+            for name in ("index", "nearest", "n_accept"):
+                out[name] = out[name].to(torch.int64)
+        else:
+            out = _mc.classify_composed(Xd, fits, decs, y_index=ydev, distances=distances)
+        cls_dev = torch.from_numpy(np.asarray(classes).astype(np.int64)).to(dev)
+        label = torch.where(out["index"] < 0, torch.full_like(out["index"], int(none_label)),
+                            cls_dev[out["index"].clamp(min=0)])
+        res = ClassifyResult(pred=out["pred"], ratio=out["ratio"], index=out["index"], label=label,
+                             nearest=out["nearest"], n_accept=out["n_accept"], T2=out["T2"], Q=out["Q"],
+                             table=out["table"], accept_counts=out["accept_counts"],
+                             n_accept_hist=out["n_accept_hist"])
+        if yi is not None:
+            table, acc = _np(res.table), _np(res.accept_counts)
+            res.metrics = {cls: _rates(*_mc.confusion_from_counts(table, acc, i)) for i, cls in enumerate(classes)}
+        if not _is_dev(X):
+            for name in ("pred", "ratio", "index", "label", "nearest", "n_accept", "T2", "Q", "table",
+                         "accept_counts", "n_accept_hist"):
+                v = getattr(res, name)
+                if v is not None:
+                    setattr(res, name, _np(v, self._out_dtype if name == "Q" else None))
+        return res
+
+    def model_distance(self, X, y):
+        """(C, C) float64 NumPy array: Wold's distance between the class models
+        (Wold & Sjöström 1977) on the labelled rows (X, y), from one
+        ``classify(X, distances=True)``: with ``Q_q(x)`` the residual of x against
+        the model of class q, ``n_r`` the rows of class r and ``k_q`` the
+        components of class q,
+          s²[r|q] = Σ_{i∈r} Q_q(x_i) / (n_r·(p − k_q))            r ≠ q
+          s²[q|q] = Σ_{i∈q} Q_q(x_i) / ((n_q − k_q − 1)·(p − k_q))
+          D[a, b] = sqrt((s²[a|b] + s²[b|a]) / (s²[a|a] + s²[b|b])),  D[a, a] = 1.
+        The sums over the rows are formed in fp64 on the device.  Rows of no
+        modelled class are ignored."""
+        from ocm import multiclass as _mc
+
+        classes, m, yi = self._classify_check(X, y, "model_distance")
+        Xd = engine.as_device_x(X)
+        res = self.classify(Xd, distances=True)
+        C = len(classes)
+        ydev = torch.from_numpy(yi.astype(np.int64)).to(res.Q.device)
+        onehot = torch.zeros((m, C + 1), dtype=torch.float64, device=res.Q.device)
+        onehot[torch.arange(m, device=res.Q.device), ydev] = 1.0
+        S = onehot[:, :C].T @ res.Q.to(torch.float64)  # S[r, q] = Σ_{i∈r} Q_q(x_i)
+        n = np.bincount(yi, minlength=C + 1)[:C]
+        return _mc.wold_distance(_np(S), n, [int(self._fits[cls].k) for cls in classes], int(self.n_features_in_))
 
     # ------------------------------------------------------ object decisions
     def predict_objects(self, X, objects=None, offsets=None, rule="vote", min_fraction=0.5, y_true=None):
