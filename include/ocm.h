@@ -818,6 +818,66 @@ int ocm_score_multi_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t
                         double* accept_out, int64_t accept_stride, int8_t* index_out, uint8_t* nearest_out,
                         uint8_t* naccept_out, const uint8_t* y_true, int64_t* counts_out, void* stream);
 
+/* ---- ROC AUC, ROC points and a keys-only sort (appended; the ABI version stays 12) ----
+ * The reference scores a trial without a threshold: roc_auc_score(labels_true, f_all)
+ * (optim_bce_nuts.py:241,279).  These entries turn scores that are already on the device into the exact
+ * AUC, into points of the ROC curve, or into their sorted copy.
+ *
+ * Every value input takes dtype 0 = float64 or 1 = float32 and is addressed in elements as
+ *   S[c·col_stride + r·row_stride]   (c < ncol, r < m; strides ≥ 0),
+ * so an (m, C) matrix and a (ncfg, m) table are both read in place.  m, n < 2^31.
+ *
+ * ocm_roc_tile_keys: the keys one workgroup ranks per sort tile.
+ *
+ * ocm_sort_f: out [dev] ncol × n contiguous, same dtype: the ascending sorted copy of each column, keys
+ *   only.  The order is that of the okey64 / okey32 keys of ocm_percentile (−0.0 before +0.0); NaNs go
+ *   last, as in np.sort, and come out as one canonical NaN.  n = 0 is a no-op.
+ *
+ * ocm_auc: positive [dev] m bytes (non-zero = positive), shared by the columns.  u2_out [dev] ncol
+ *   uint64: u2 = Σ over (positive i, negative j) of 2·[s_i > s_j] + [s_i == s_j], compared by value
+ *   (−0.0 == +0.0, ±inf in order, a float32 score as its exact double), so AUC = u2 / (2·P·N), the
+ *   trapezoid AUC with scikit-learn's tie rule.  np_out [dev] 2 int64 {P, N} (every row counts, NaN or
+ *   not).  nnan_out [dev, nullable] ncol int64: the NaN scores of each column; those rows are left out of
+ *   that column's u2.  m = 0, P = 0 or N = 0 give u2 = 0 and success.
+ *
+ * ocm_roc_counts: thr [dev] ncol × K float64, ascending per column, 1 ≤ K ≤ 4096 (else OCM_ERR_ARG);
+ *   cnt_out [dev] ncol × K × 2 uint64: {positives with s ≥ thr, negatives with s ≥ thr}, the same value
+ *   comparison; a NaN score counts nowhere.  ncol ≤ 65535.  Workspace: ncol · 2 · (K + 1) uint64.
+ *
+ * ocm_roc_last_passes: the radix passes the calling thread's last ocm_sort_f / ocm_auc executed (the most
+ *   over its column groups), out of 8 (float64) or 4 (float32).
+ *
+ * How: ocm_auc sorts the keys of the smaller class only (no payload), folding −0.0 into +0.0; each row of
+ *   the other class is read from S through the mask and finds lt = #keys < s and le = #keys ≤ s in the
+ *   sorted side by binary searches with no branch on the data (bucket splitters in LDS, then inside one
+ *   bucket; le by two probes behind lt, by a second search only in a wave that meets a longer run of equal
+ *   keys): with the negatives sorted it adds 2·lt + (le − lt), with the positives sorted
+ *   2·(P − le) + (le − lt).  64-bit integer sums, one integer atomic per workgroup.  The sort is an LSD
+ *   radix sort on 8-bit digits: one read histograms every digit position of every column, a position
+ *   whose digit is the same for all keys of a column is skipped for that column, and an executed pass is
+ *   three launches (tile histograms, a scan over (digit, tile), a stable scatter ranked by 64-bit
+ *   __ballot masks); the first executed pass gathers the sorted class out of S.  No workgroup waits for
+ *   another, no floating-point atomics: every output is an integer or a permutation of its input, and
+ *   two calls on one input give the same bytes.  Columns are a grid dimension.  Both entries wait for
+ *   the stream (ocm_auc twice, ocm_sort_f once per column group) to read the class sizes and the passes
+ *   to run.
+ * Workspace of ocm_sort_f and ocm_auc, per column of a group, with n_s the keys sorted (n, or the smaller
+ *   class) and b the key bytes (8 or 4): 2·n_s·b + (⌈m/2048⌉ + b)·1 KiB + 24 bytes, and 32 KiB more for
+ *   ocm_auc (the last key of each of ≤ 32 KiB / b buckets of the sorted side, which its search keeps in
+ *   LDS so that only the steps inside one bucket go to memory).  Columns are processed
+ *   in groups of ⌊2^26 / max(n_s, m/8)⌋ (at least one, at most 65535), which keeps a group's workspace
+ *   near 1 GiB. */
+int ocm_roc_tile_keys(void);
+int ocm_roc_last_passes(void);
+int ocm_sort_f(ocm_ctx* ctx, const void* v, int32_t dtype, int64_t n, int64_t ncol, int64_t col_stride,
+               int64_t row_stride, void* out, void* stream);
+int ocm_auc(ocm_ctx* ctx, const void* S, int32_t dtype, int64_t m, int64_t ncol, int64_t col_stride,
+            int64_t row_stride, const uint8_t* positive, uint64_t* u2_out, int64_t* np_out, int64_t* nnan_out,
+            void* stream);
+int ocm_roc_counts(ocm_ctx* ctx, const void* S, int32_t dtype, int64_t m, int64_t ncol, int64_t col_stride,
+                   int64_t row_stride, const uint8_t* positive, const double* thr, int32_t K, uint64_t* cnt_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,13 @@ SIGNATURES = {
                                     ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(OcmDecision), c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "ocm_roc_tile_keys": (c_i32, []),
+    "ocm_roc_last_passes": (c_i32, []),
+    "ocm_sort_f": (c_i32, [c_void_p, c_void_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p]),
+    "ocm_auc": (c_i32, [c_void_p, c_void_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_void_p]),
+    "ocm_roc_counts": (c_i32, [c_void_p, c_void_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_i32,
+                               c_void_p, c_void_p]),
     "ocm_bn_scratch_bytes": (ctypes.c_size_t, [c_i32]),
     "ocm_bn_fwd_train": (c_i32, [c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, ctypes.c_float,
                                  ctypes.c_float, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,

@@ -428,6 +428,45 @@ class SIMCA(BaseEstimator, ClassifierMixin):
             out = gather_rows(out, shard[2])
         return out if _is_dev(X) else out.cpu().numpy()
 
+    # ------------------------------------------------ threshold-free evaluation
+    def _roc_classes(self, cls, who):
+        if cls is None:
+            return list(enumerate(self.model_class))
+        for i, c in enumerate(self.model_class):
+            if c == cls:
+                return [(i, c)]
+        raise ValueError(f"{who}: class {cls!r} was not fitted (fitted: {list(self.model_class)})")
+
+    def _roc_scores(self, X, y_true, who):
+        D = self.decision_function(X if _is_dev(X) else engine.as_device_x(X))
+        yt = _host_labels(y_true)
+        if yt.shape != (D.shape[0],):
+            raise ValueError(f"{who}: y_true has shape {yt.shape}, X has {D.shape[0]} rows")
+        return D, yt
+
+    def roc_auc(self, X, y_true, cls=None):
+        """Exact ROC AUC of every fitted class as a one-class model: class i's
+        column of ``decision_function(X)`` (bit for bit, kept on the device)
+        against ``y_true == cls_i`` (``ocm.roc.auc``).  ``cls`` given: that
+        class's ``AucResult``; otherwise a dict {class: AucResult}.  The
+        reference's threshold-free figure, roc_auc_score (optim_bce_nuts.py:241)."""
+        from ocm import roc
+
+        D, yt = self._roc_scores(X, y_true, "roc_auc")
+        out = {c: roc.auc(D[:, i], yt == c) for i, c in self._roc_classes(cls, "roc_auc")}
+        return out[cls] if cls is not None else out
+
+    def roc_points(self, X, y_true, cls=None, n_points=257):
+        """Exact ROC points of every fitted class on an even FPR grid
+        (``ocm.roc.roc_points`` on the columns of ``decision_function(X)``):
+        a ``RocPoints`` for ``cls``, else a dict {class: RocPoints}."""
+        from ocm import roc
+
+        D, yt = self._roc_scores(X, y_true, "roc_points")
+        out = {c: roc.roc_points(D[:, i], yt == c, n_points=n_points)
+               for i, c in self._roc_classes(cls, "roc_points")}
+        return out[cls] if cls is not None else out
+
     def contributions(self, X, cls=None, groups=None, matrices=False):
         """Contribution plots of class ``cls`` (default: the only class) for the
         rows of X, extending utils/SIMCA.py:67-71: the residual
