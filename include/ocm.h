@@ -427,6 +427,38 @@ int ocm_rowfit_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t
 /* One read and one write of X: out [dev] m × p (ldo ≥ p) = the corrected rows; coef_out as above (nullable). */
 int ocm_emsc_apply_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, const double* W,
                        const double* B, int32_t q, float* out, int64_t ldo, float* coef_out, void* stream);
+/* ---- baseline correction: Whittaker smoother and asymmetric least squares (Eilers & Boelens 2005) ----
+ * D is the d-th order difference matrix, np.diff(np.eye(p), d, axis=0), d ∈ {1, 2}; λ > 0.
+ *   Whittaker: for a row x (float32, read as fp64) and weights w ≥ 0, z solves
+ *       (diag(w) + λ·DᵀD) z = w ∘ x
+ *     a symmetric system of half bandwidth d, positive definite when at least d weights are positive.
+ *   AsLS(λ, asym, n_iter): w⁽¹⁾ = 1; for it = 1..n_iter, z⁽ⁱᵗ⁾ is the Whittaker solve of x under w⁽ⁱᵗ⁾ and
+ *       w⁽ⁱᵗ⁺¹⁾_j = asym if x_j > z⁽ⁱᵗ⁾_j else 1 − asym
+ *     (compared in fp64 on the unrounded z; an exact tie takes 1 − asym, where Eilers' code gives 0: the
+ *     matrix stays positive definite).  A row stops once an update leaves all its weights unchanged
+ *     (further solves would repeat bit for bit); iters is the number of solves the row ran.  The result
+ *     is the baseline z of the last solve, or x − z formed in fp64, rounded once to float32.
+ * Numerics: LDLᵀ without pivoting, every recurrence in fp64 (the systems reach condition numbers of 1e8
+ * and more at ordinary settings), one lane per row in one fixed order: the same bits on every launch,
+ * for any m, any position of the row in the matrix and any ldx / ldo.  No atomics but the nbad count.
+ * A row whose pivot is not a positive finite number, or with a negative or NaN weight, or with fewer
+ * than d positive weights, is written as NaN and counted in nbad_out; no other row is affected.
+ * Workspace: a workgroup's 64 rows keep (d + 1)·8 bytes per element (8 under shared weights) for the
+ * back substitution, AsLS one bit more.  The grid is at most 8 workgroups per CU and walks over the
+ * 64-row blocks, so the workspace depends on the device and on p (at most CUs·8·64·p·(8·(d + 1) + 1/8)
+ * bytes), not on m: 2M rows need no more than 1M.
+ * X [dev] m × p float32 (ldx ≥ p, any 4-byte alignment), out [dev] m × p float32 (ldo ≥ p), not
+ * overlapping X.  OCM_ERR_ARG for d ∉ {1, 2}, p < d + 1, λ not positive and finite, ldx or ldo < p,
+ * m ≥ 2³¹. */
+/* W [dev]: NULL: w = 1; ldw = 0: one (p) vector for all rows; ldw ≥ p: (m, p) per row.  With shared weights
+ * the matrix is factorised once and a row costs one read, one write and 16 bytes of workspace traffic per
+ * element.  nbad_out [dev] one int32 (nullable). */
+int ocm_whittaker_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, const float* W, int64_t ldw,
+                      double lam, int32_t d, float* out, int64_t ldo, int32_t* nbad_out, void* stream);
+/* subtract 0: out = the baseline z, 1: out = x − z.  iters_out [dev] m int32 (nullable).  Also
+ * OCM_ERR_ARG for asym ∉ (0, 1) or n_iter < 1. */
+int ocm_asls_f32(ocm_ctx* ctx, const float* X, int64_t ldx, int64_t m, int32_t p, double lam, double asym, int32_t d,
+                 int32_t n_iter, int32_t subtract, float* out, int64_t ldo, int32_t* iters_out, void* stream);
 /* ocm_colmean_f32 / ocm_gram_f32_ex / ocm_score_f32_diag on the preprocessed rows, read raw from X.
  * The default i8×3 Gram applies the transform in its quantiser (halo columns staged through LDS) and
  * k_score_1p applies it to each row tile in registers as the tile arrives (p ∈ {256, 512, 1024, 2048},

@@ -205,6 +205,10 @@ SIGNATURES = {
                                c_void_p]),
     "ocm_emsc_apply_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                    c_i64, c_void_p, c_void_p]),
+    "ocm_whittaker_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_i64, c_f64, c_i32, c_void_p,
+                                  c_i64, c_void_p, c_void_p]),
+    "ocm_asls_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_f64, c_f64, c_i32, c_i32, c_i32, c_void_p,
+                             c_i64, c_void_p, c_void_p]),
     "ocm_colmean_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                      c_void_p]),
     "ocm_gram_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p,

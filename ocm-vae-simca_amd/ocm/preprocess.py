@@ -29,7 +29,7 @@ from ._lib import Context, check, ptr
 from .prepview import PrepView
 
 __all__ = ["savgol_taps", "snv_savgol", "snv", "savgol_filter", "mahalanobis_outlier_mask", "PrepView",
-           "MSC", "EMSC", "scatter_basis", "scatter_weights"]
+           "MSC", "EMSC", "scatter_basis", "scatter_weights", "whittaker_bands", "whittaker", "asls", "AsLS"]
 
 
 @functools.lru_cache(maxsize=64)
@@ -320,6 +320,188 @@ class MSC(EMSC):
 
     def __init__(self, reference=None):
         super().__init__(degree=0, reference=reference)
+
+
+def whittaker_bands(p: int, d: int = 2) -> np.ndarray:
+    """The (d + 1, p) fp64 lower-banded form of DᵀD, D the d-th difference
+    matrix ``np.diff(np.eye(p), d, axis=0)``, as
+    ``scipy.linalg.solveh_banded(..., lower=True)`` takes it: row k holds the
+    k-th sub-diagonal, padded with zeros at the end.  A pure host function."""
+    p, d = int(p), int(d)
+    if d not in (1, 2):
+        raise ValueError("baseline: d must be 1 or 2")
+    if p < d + 1:
+        raise ValueError(f"baseline: p = {p} columns are too few for differences of order d = {d} (p >= d + 1)")
+    j = np.arange(p)
+    ab = np.zeros((d + 1, p), dtype=np.float64)
+    if d == 1:
+        ab[0] = (j >= 1).astype(float) + (j <= p - 2)
+        ab[1, :p - 1] = -1.0
+    else:
+        first, mid, last = j <= p - 3, (j >= 1) & (j <= p - 2), j >= 2  # the rows of D that touch column j
+        ab[0] = first + 4.0 * mid + last
+        ab[1] = -2.0 * (first.astype(float) + mid)
+        ab[2] = first
+    return ab
+
+
+def _baseline_shape(who: str, X, lam, d) -> tuple[int, int]:
+    """The checks of λ, d and the shape of X, before any device work."""
+    lam, d = float(lam), int(d)
+    if not (np.isfinite(lam) and lam > 0.0):
+        raise ValueError(f"{who}: lam must be positive and finite, got {lam}")
+    if d not in (1, 2):
+        raise ValueError(f"{who}: d must be 1 or 2, got {d}")
+    shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
+    if len(shape) != 2:
+        raise ValueError(f"{who}: X must be a (m, p) matrix, got shape {shape}")
+    if shape[1] < d + 1:
+        raise ValueError(f"{who}: p = {shape[1]} columns are too few for differences of order d = {d} (p >= d + 1)")
+    return int(shape[0]), int(shape[1])
+
+
+def _extent(t: torch.Tensor) -> tuple[int, int]:
+    """[first, last) byte of a 2-D tensor's elements."""
+    n = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1 if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def _baseline_out(who: str, out, X, m: int, p: int):
+    """``out`` must be a (m, p) float32 device tensor with unit column stride
+    that shares no memory with X; checked before any device work."""
+    if out is None:
+        return
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, p):
+        raise ValueError(f"{who}: out must be a ({m}, {p}) tensor, got "
+                         f"{tuple(out.shape) if hasattr(out, 'shape') else type(out).__name__}")
+    if out.dtype != torch.float32:
+        raise ValueError(f"{who}: out must be float32, got {out.dtype}")
+    if out.stride(1) != 1 or out.stride(0) < p:
+        raise ValueError(f"{who}: out must have unit column stride and a row stride >= p")
+    src = X.X if isinstance(X, PrepView) else X
+    if isinstance(src, torch.Tensor) and src.device == out.device:
+        (a0, a1), (b0, b1) = _extent(src), _extent(out)
+        if a0 < b1 and b0 < a1:
+            raise ValueError(f"{who}: out overlaps X (the rows are read again after the first are written)")
+    if not out.is_cuda or (isinstance(src, torch.Tensor) and src.is_cuda and src.device != out.device):
+        raise ValueError(f"{who}: out must be on the device of X, got {out.device}")
+
+
+def _baseline_weights(weights, m: int, p: int, d: int):
+    """None, or the weights as given with their kind ("vector" / "rows").
+    Host weights are checked here; device weights are checked by the kernel
+    (a bad row is counted and ``whittaker`` raises)."""
+    if weights is None:
+        return None, None
+    on_device = isinstance(weights, torch.Tensor) and weights.is_cuda
+    w = weights if on_device else np.asarray(weights.numpy() if isinstance(weights, torch.Tensor) else weights)
+    shape = tuple(w.shape)
+    if shape not in ((p,), (m, p)):
+        raise ValueError(f"whittaker: weights must be None, ({p},) or ({m}, {p}), got shape {shape}")
+    kind = "vector" if shape == (p,) else "rows"  # m == 1 and a (p,) vector: the shared path
+    if not on_device:
+        w = w.astype(np.float64)
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("whittaker: weights must be finite and >= 0")
+        if kind == "vector" and int((w > 0).sum()) < d:
+            raise ValueError(f"whittaker: fewer than d = {d} positive weights: the system is singular")
+    return kind, w
+
+
+def whittaker(X, lam, d: int = 2, weights=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The Whittaker smooth of every row of a (m, p) float32 matrix
+    (include/ocm.h, baseline correction): z solves
+    (diag(w) + λ·DᵀD) z = w ∘ x in fp64 on the GPU (``ocm_whittaker_f32``),
+    D the d-th difference matrix.  ``weights``: None (w = 1), a (p,) vector
+    shared by all rows (both factorise once), or a (m, p) matrix.  Raises
+    ``ValueError`` when a row's system is not positive definite (fewer than d
+    positive weights, a negative or NaN weight).  Eager only: a row's solve is
+    global along the wavelengths, it cannot run inside another kernel's loads,
+    so there is no lazy view."""
+    m, p = _baseline_shape("whittaker", X, lam, d)
+    kind, w = _baseline_weights(weights, m, p, int(d))
+    _baseline_out("whittaker", out, X, m, p)
+    Xd = _device_rows(X)
+    W, ldw = None, 0
+    if kind is not None:
+        W = (w if isinstance(w, torch.Tensor) else torch.from_numpy(w)).to(device=Xd.device, dtype=torch.float32)
+        if kind == "vector":
+            W = W.contiguous()
+        else:
+            if W.stride(1) != 1 or W.stride(0) < p:
+                W = W.contiguous()
+            ldw = W.stride(0)
+    if out is None:
+        out = torch.empty((m, p), dtype=torch.float32, device=Xd.device)
+    nbad = torch.zeros(1, dtype=torch.int32, device=Xd.device)
+    check(_lib.load().ocm_whittaker_f32(Context.get(Xd.device.index).handle, ptr(Xd), Xd.stride(0), m, p, ptr(W), ldw,
+                                        float(lam), int(d), ptr(out), out.stride(0), ptr(nbad),
+                                        engine._stream(Xd.device)), "ocm_whittaker_f32")
+    bad = int(nbad.item())
+    if bad:
+        raise ValueError(f"whittaker: {bad} of {m} rows have a system that is not positive definite (fewer than "
+                         f"d = {int(d)} positive weights, or a negative or NaN weight); they were written as NaN")
+    return out
+
+
+def asls(X, lam: float = 1e5, asym: float = 0.01, n_iter: int = 10, d: int = 2, subtract: bool = True,
+         out: torch.Tensor | None = None, return_iters: bool = False):
+    """Asymmetric least squares baseline (Eilers & Boelens 2005; include/ocm.h,
+    baseline correction) of every row of a (m, p) float32 matrix, all
+    iterations of a row in one kernel (``ocm_asls_f32``): start from w = 1,
+    smooth (``whittaker``), set w_j = asym where x_j > z_j and 1 − asym
+    elsewhere (a tie included), at most ``n_iter`` solves; a row stops when its
+    weights no longer change.  Returns the corrected rows x − z
+    (``subtract=True``) or the baselines z, float32 on the device, and with
+    ``return_iters`` the (m,) int32 number of solves each row ran.  Eager only:
+    a row's solve is global along the wavelengths, there is no lazy view."""
+    m, p = _baseline_shape("asls", X, lam, d)
+    asym = float(asym)
+    if not (0.0 < asym < 1.0):
+        raise ValueError(f"asls: asym must lie in (0, 1), got {asym}")
+    if int(n_iter) < 1:
+        raise ValueError(f"asls: n_iter must be >= 1, got {n_iter}")
+    _baseline_out("asls", out, X, m, p)
+    Xd = _device_rows(X)
+    if out is None:
+        out = torch.empty((m, p), dtype=torch.float32, device=Xd.device)
+    iters = torch.empty(m, dtype=torch.int32, device=Xd.device) if return_iters else None
+    check(_lib.load().ocm_asls_f32(Context.get(Xd.device.index).handle, ptr(Xd), Xd.stride(0), m, p, float(lam), asym,
+                                   int(d), int(n_iter), 1 if subtract else 0, ptr(out), out.stride(0), ptr(iters),
+                                   engine._stream(Xd.device)), "ocm_asls_f32")
+    return (out, iters) if return_iters else out
+
+
+class AsLS:
+    """``asls`` as an estimator, in the style of ``MSC`` / ``EMSC``: nothing is
+    learned (``fit`` is a no-op), ``transform(X)`` returns the corrected rows
+    x − z and ``baseline(X)`` the baselines z; ``iters_`` holds the (m,) int32
+    number of solves per row of the last call.  Eager only (no lazy view)."""
+
+    def __init__(self, lam: float = 1e5, asym: float = 0.01, n_iter: int = 10, d: int = 2):
+        self.lam, self.asym, self.n_iter, self.d = float(lam), float(asym), int(n_iter), int(d)
+        if not (np.isfinite(self.lam) and self.lam > 0.0):
+            raise ValueError(f"AsLS: lam must be positive and finite, got {self.lam}")
+        if not (0.0 < self.asym < 1.0):
+            raise ValueError(f"AsLS: asym must lie in (0, 1), got {self.asym}")
+        if self.n_iter < 1:
+            raise ValueError(f"AsLS: n_iter must be >= 1, got {self.n_iter}")
+        if self.d not in (1, 2):
+            raise ValueError(f"AsLS: d must be 1 or 2, got {self.d}")
+        self.iters_ = None
+
+    def fit(self, X=None, y=None):
+        return self
+
+    def _run(self, X, subtract):
+        out, self.iters_ = asls(X, self.lam, self.asym, self.n_iter, self.d, subtract=subtract, return_iters=True)
+        return out
+
+    def transform(self, X) -> torch.Tensor:
+        return self._run(X, True)
+
+    def baseline(self, X) -> torch.Tensor:
+        return self._run(X, False)
 
 
 def mahalanobis_outlier_mask(X, n_components: int, percentile: float = 95.0, rows=None):
