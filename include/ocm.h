@@ -910,6 +910,65 @@ int ocm_roc_counts(ocm_ctx* ctx, const void* S, int32_t dtype, int64_t m, int64_
                    int64_t row_stride, const uint8_t* positive, const double* thr, int32_t K, uint64_t* cnt_out,
                    void* stream);
 
+/* ---- sample selection: Kennard–Stone and Duplex (appended; the ABI version stays 12) ----
+ * Choosing the calibration rows in place of a random train_test_split (simca_nuts.py:73-74,
+ * utils/data_utils.py): Kennard & Stone's max–min selection and Snee's Duplex, on a coordinate matrix
+ * Z [dev] n × q (float32 or float64, ldz ≥ q, read in place, every value taken as its exact double).
+ *   d2(i, j) = Σ_c w_c (z_ic − z_jc)²  in fp64, in the difference form (never |a|² + |b|² − 2a·b),
+ *   c ascending: t = z_ic − z_jc, acc = fma(w_c·t, t, acc).  w [dev] q doubles ≥ 0, NULL: all 1
+ *   (pass 1/λ for a Mahalanobis distance on PCA scores).  Every kernel forms d2 this one way, so a
+ *   distance has the same bits in every entry and on both selection paths; plain fp64 VALU (the work
+ *   is bound by launches and cache latency, not FLOPs).
+ * Candidates compare under one total order (value descending, then i ascending, then j ascending) at
+ * every level, so no result depends on tile shape or grid size, and two calls give the same bytes.
+ * A row with a non-finite coordinate is an argument error of the caller: the kernels count such rows
+ * into nbad_out [dev] one int32 (required) and the other outputs are then unspecified (ocm_ks_select:
+ * left untouched).  Everything is ordered on `stream`; no entry waits for the device (but a workspace
+ * that has to grow drains the stream first: ocm_ctx_reserve pre-sizes it).  No workgroup waits for
+ * another, no cooperative launch, no fences; the only atomic is the bad-row count.
+ *
+ * ocm_ks_pair_f32 / _f64: the farthest pair.  (i*, j*) = argmax of d2 over i < j among the rows with
+ *   skip[i] == 0 (skip [dev] n bytes, NULL: none), ties to the smallest i, then the smallest j;
+ *   pair_out [dev] 2 int64, d2_out [dev] one double ({−1, −1} and NaN when fewer than two rows are
+ *   left).  One workgroup per pair of 128-row tiles of the upper triangle, both panels staged through
+ *   LDS in 16-column chunks (any q), one partial per workgroup, then reduction launches of 4096
+ *   partials per workgroup.  n ≥ 2.  OCM_ERR_ARG when the tile pairs exceed the grid limit (n above
+ *   ≈ 8.3M).  Workspace: 24 bytes per tile pair.
+ *
+ * ocm_ks_nearest_f32 / _f64: idx_out [dev] one int64 = argmin_i Σ_c w_c (z_ic − center_c)², ties to the
+ *   smallest i, and d2_out that value (center [dev] q doubles: the column mean for the "mean" start).
+ *
+ * ocm_ks_select_f32 / _f64: all steps of Kennard–Stone (n_b = 0) or Duplex (n_b > 0) after the starts.
+ *   start_a [dev] n_start_a ≥ 1 distinct rows (and start_b, n_start_b for Duplex; the two lists
+ *   disjoint): order_a [dev] n_a int64 begins with them and their d2_a [dev] n_a doubles is NaN.
+ *   Step: m_i = min over the set's members s of d2(i, s); the next member is the argmax of m_i over the
+ *   rows in no set, ties to the smallest i (m = 0 is a valid maximum: selection runs on through
+ *   duplicates), and its d2 entry is that m.  Duplex: the sets take turns, A first, each by the
+ *   distance to its own members; a full set is skipped.  n_a + n_b ≤ n.  A start index outside [0, n)
+ *   adds 2^30 to nbad_out and nothing is written.
+ *   path 0 auto, 1 small, 2 wide (tests force each).  small: one workgroup, the min distances (and Z,
+ *   when it fits beside them) in LDS, all steps in one launch, one barrier per step; OCM_ERR_ARG when
+ *   the min distances alone exceed the LDS.  wide: one launch per pick; each workgroup reduces the
+ *   previous launch's ≤ 1024 partials itself, applies that pick to its rows and writes its partial to
+ *   the other half of a ping-pong buffer; a last small launch records the final pick and the starts.
+ *   Workspace (wide): 8 bytes per row and set, and 48 KiB. */
+int ocm_ks_pair_f32(ocm_ctx* ctx, const float* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                    const uint8_t* skip, int64_t* pair_out, double* d2_out, int32_t* nbad_out, void* stream);
+int ocm_ks_pair_f64(ocm_ctx* ctx, const double* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                    const uint8_t* skip, int64_t* pair_out, double* d2_out, int32_t* nbad_out, void* stream);
+int ocm_ks_nearest_f32(ocm_ctx* ctx, const float* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                       const double* center, int64_t* idx_out, double* d2_out, int32_t* nbad_out, void* stream);
+int ocm_ks_nearest_f64(ocm_ctx* ctx, const double* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                       const double* center, int64_t* idx_out, double* d2_out, int32_t* nbad_out, void* stream);
+int ocm_ks_select_f32(ocm_ctx* ctx, const float* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                      const int64_t* start_a, int64_t n_start_a, int64_t n_a, const int64_t* start_b,
+                      int64_t n_start_b, int64_t n_b, int64_t* order_a, double* d2_a, int64_t* order_b, double* d2_b,
+                      int32_t* nbad_out, int32_t path, void* stream);
+int ocm_ks_select_f64(ocm_ctx* ctx, const double* Z, int64_t ldz, int64_t n, int32_t q, const double* w,
+                      const int64_t* start_a, int64_t n_start_a, int64_t n_a, const int64_t* start_b,
+                      int64_t n_start_b, int64_t n_b, int64_t* order_a, double* d2_a, int64_t* order_b, double* d2_b,
+                      int32_t* nbad_out, int32_t path, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

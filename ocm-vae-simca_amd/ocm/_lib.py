@@ -209,6 +209,20 @@ SIGNATURES = {
                                   c_i64, c_void_p, c_void_p]),
     "ocm_asls_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_f64, c_f64, c_i32, c_i32, c_i32, c_void_p,
                              c_i64, c_void_p, c_void_p]),
+    "ocm_ks_pair_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "ocm_ks_pair_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "ocm_ks_nearest_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "ocm_ks_nearest_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "ocm_ks_select_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_i64,
+                                  c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                  c_void_p]),
+    "ocm_ks_select_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_i64,
+                                  c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                  c_void_p]),
     "ocm_colmean_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                      c_void_p]),
     "ocm_gram_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p,

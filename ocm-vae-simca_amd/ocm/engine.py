@@ -449,6 +449,115 @@ def segment_sums(X, offsets, checked: bool = False) -> torch.Tensor:
     return out
 
 
+def _ks_inputs(who: str, Z, w):
+    """(Z read in place where its strides allow, ldz, w) for the ocm_ks_* entries."""
+    if not (isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dim() == 2 and
+            Z.dtype in (torch.float32, torch.float64)):
+        raise ValueError(f"{who}: Z must be a 2-D float32 or float64 device tensor")
+    n, q = Z.shape
+    if n < 1 or q < 1:
+        raise ValueError(f"{who}: Z has shape {tuple(Z.shape)}")
+    if (q > 1 and Z.stride(1) != 1) or (n > 1 and Z.stride(0) < q):
+        Z = Z.contiguous()
+    ldz = Z.stride(0) if n > 1 else q
+    if w is not None:
+        w = torch.as_tensor(w, dtype=torch.float64).to(Z.device).contiguous()
+        if tuple(w.shape) != (q,):
+            raise ValueError(f"{who}: w has shape {tuple(w.shape)}, Z has {q} columns")
+    return Z, ldz, w
+
+
+def _ks_fn(name: str, Z):
+    fn = f"ocm_ks_{name}_f64" if Z.dtype == torch.float64 else f"ocm_ks_{name}_f32"
+    return fn, getattr(_lib.load(), fn)
+
+
+def ks_pair(Z: torch.Tensor, w=None, skip: torch.Tensor | None = None):
+    """The farthest pair of the rows of Z (ocm_ks_pair_f32 / _f64): (pair (2,) int64,
+    d2 (1,) float64, nbad (1,) int32), device tensors, nothing read back.  ``w``: (q,)
+    column weights; ``skip``: (n,) uint8 device mask of rows left out."""
+    Z, ldz, w = _ks_inputs("ks_pair", Z, w)
+    n, q = Z.shape
+    dev = Z.device
+    if skip is not None:
+        if not (skip.is_cuda and skip.dtype == torch.uint8 and tuple(skip.shape) == (n,)):
+            raise ValueError("ks_pair: skip must be an (n,) uint8 device tensor")
+        skip = skip.contiguous()
+    pair = torch.empty(2, dtype=torch.int64, device=dev)
+    d2 = torch.empty(1, dtype=torch.float64, device=dev)
+    nbad = torch.empty(1, dtype=torch.int32, device=dev)
+    name, fn = _ks_fn("pair", Z)
+    check(fn(Context.get(dev.index).handle, ptr(Z), ldz, n, q, ptr(w), ptr(skip), ptr(pair), ptr(d2), ptr(nbad),
+             _stream(dev)), name)
+    return pair, d2, nbad
+
+
+def ks_nearest(Z: torch.Tensor, center: torch.Tensor, w=None):
+    """The row of Z nearest to ``center`` ((q,) float64 device tensor): (index (1,)
+    int64, d2 (1,) float64, nbad (1,) int32), device tensors (ocm_ks_nearest_*)."""
+    Z, ldz, w = _ks_inputs("ks_nearest", Z, w)
+    n, q = Z.shape
+    dev = Z.device
+    center = center.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(center.shape) != (q,):
+        raise ValueError(f"ks_nearest: center has shape {tuple(center.shape)}, Z has {q} columns")
+    idx = torch.empty(1, dtype=torch.int64, device=dev)
+    d2 = torch.empty(1, dtype=torch.float64, device=dev)
+    nbad = torch.empty(1, dtype=torch.int32, device=dev)
+    name, fn = _ks_fn("nearest", Z)
+    check(fn(Context.get(dev.index).handle, ptr(Z), ldz, n, q, ptr(w), ptr(center), ptr(idx), ptr(d2), ptr(nbad),
+             _stream(dev)), name)
+    return idx, d2, nbad
+
+
+def ks_select(Z: torch.Tensor, start_a: torch.Tensor, n_a: int, start_b: torch.Tensor | None = None, n_b: int = 0,
+              w=None, path: int = 0, out: dict | None = None) -> dict:
+    """All steps of Kennard–Stone (``n_b == 0``) or Duplex after the starts
+    (ocm_ks_select_f32 / _f64).  ``start_a`` / ``start_b``: int64 device tensors of
+    distinct row indices (not checked on the host: they may come from ``ks_pair``).
+    Returns device tensors ``order_a`` (n_a,) int64, ``d2_a`` (n_a,) float64 (NaN at
+    the starts), ``order_b`` / ``d2_b`` (None without a second set) and ``nbad`` (1,)
+    int32; nothing is read back.  ``out``: tensors to write into (the same keys).
+    ``path``: 0 auto, 1 the one-workgroup LDS path, 2 one launch per pick (tests)."""
+    Z, ldz, w = _ks_inputs("ks_select", Z, w)
+    n, q = Z.shape
+    dev = Z.device
+    n_a, n_b = int(n_a), int(n_b)
+
+    def starts(t, name):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+            raise ValueError(f"ks_select: {name} must be a 1-D int64 device tensor")
+        return t.contiguous()
+
+    start_a = starts(start_a, "start_a")
+    nsa, nsb = start_a.numel(), 0
+    if n_b > 0:
+        start_b = starts(start_b, "start_b")
+        nsb = start_b.numel()
+    else:
+        start_b = None
+    if not (1 <= nsa <= n_a) or (n_b > 0 and not (1 <= nsb <= n_b)) or n_b < 0 or n_a + n_b > n:
+        raise ValueError(f"ks_select: sizes ({n_a}, {n_b}) with ({nsa}, {nsb}) starts do not fit {n} rows")
+    out = dict(out or {})
+
+    def buf(key, size, dtype):
+        t = out.get(key)
+        if t is None:
+            t = out[key] = torch.empty(size, dtype=dtype, device=dev)
+        elif not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (size,) and t.is_contiguous()):
+            raise ValueError(f"ks_select: out[{key!r}] must be a contiguous ({size},) {dtype} device tensor")
+        return t
+
+    order_a, d2_a = buf("order_a", n_a, torch.int64), buf("d2_a", n_a, torch.float64)
+    order_b = buf("order_b", n_b, torch.int64) if n_b > 0 else None
+    d2_b = buf("d2_b", n_b, torch.float64) if n_b > 0 else None
+    nbad = buf("nbad", 1, torch.int32)
+    name, fn = _ks_fn("select", Z)
+    check(fn(Context.get(dev.index).handle, ptr(Z), ldz, n, q, ptr(w), ptr(start_a), nsa, n_a, ptr(start_b), nsb, n_b,
+             ptr(order_a), ptr(d2_a), ptr(order_b), ptr(d2_b), ptr(nbad), int(path), _stream(dev)), name)
+    return {"order_a": order_a, "d2_a": d2_a, "order_b": order_b, "d2_b": d2_b, "nbad": nbad}
+
+
 def pls_fit(S: torch.Tensor, s: torch.Tensor, A: int) -> dict:
     """The PLS recursion of nprob problems on their moments (ocm_pls_fit_f64):
     S (nprob, p, p) = XcᵀXc and s (nprob, p, M) = XcᵀYc, float64 device tensors.
