@@ -969,6 +969,41 @@ int ocm_ks_select_f64(ocm_ctx* ctx, const double* Z, int64_t ldz, int64_t n, int
                       int64_t n_start_b, int64_t n_b, int64_t* order_a, double* d2_a, int64_t* order_b, double* d2_b,
                       int32_t* nbad_out, int32_t path, void* stream);
 
+/* ---- mask morphology (appended; the ABI version stays 12) ----
+ * Eroding, dilating and measuring the object masks of "images into objects" before their spectra are
+ * read: the outer pixels of an object mix it with the belt, a specular hole inside it is lost.  One
+ * primitive gives all of it, the exact Euclidean distance transform of the mask:
+ *   d2(y, x) = min over the background pixels (y', x') of (y − y')² + (x − x')²,  0 on background.
+ * Erosion by the disc {dx² + dy² ≤ r2} is d2 > r2 (scipy.ndimage.binary_erosion, bit for bit), dilation
+ * the same on the complement, opening and closing two such calls, the depth of a pixel √d2.
+ *
+ * ocm_edt_u8: mask [dev] H × W bytes, non-zero = foreground.  d2_out [dev] H × W int32 or NULL;
+ *   mask_out [dev] H × W bytes (0 / 1) or NULL, mask_out = d2 > r2; at least one of the two.  mask_out
+ *   may alias nothing.  flags:
+ *     OCM_EDT_BORDER_BG   the pixels just outside the image are background (binary_erosion's
+ *                         border_value = 0); without it only the image's own pixels count;
+ *     OCM_EDT_INVERT_IN   zero bytes are the foreground: distances to the nearest non-zero pixel;
+ *     OCM_EDT_INVERT_OUT  mask_out = !(d2 > r2).
+ *   Without any background (and without BORDER_BG) every d2 is OCM_EDT_NONE, which mask_out takes as
+ *   greater than any r2.  Integer arithmetic alone: two calls give the same bytes.  Three launches,
+ *   whatever the image holds: (1) the background bits of every column packed 64 rows to a word, 4 mask
+ *   bytes per lane where W and the pointer allow, single bytes otherwise; (2) g(y, x), the vertical
+ *   distance to the nearest background pixel of column x, from those words by count-leading / -trailing-
+ *   zeros (no sweep along H: one thread per column and 64-row band), uint16 with 65535 for "none in this
+ *   column"; (3) one workgroup per row: the row's g staged in LDS (2 bytes per pixel and the minimum of
+ *   every 64-column segment), d2 = min over x' of (x − x')² + g(y, x')² by a scan outwards from x that
+ *   stops once (x − x')² ≥ the best so far and skips a segment whose minimum cannot improve it.  Exact;
+ *   O(H·W·min(R, W)) for objects of radius R.  No atomics, no host synchronisation, no workgroup waits
+ *   for another.  Workspace: 2 bytes per pixel and 8 bytes per column and 64 rows.  OCM_ERR_ARG, before
+ *   any pointer is looked at, for H or W < 1, H or W > 32767 (H² + W² stays below 2^31), unknown flag
+ *   bits, r2 < 0 or both outputs NULL. */
+#define OCM_EDT_BORDER_BG 1
+#define OCM_EDT_INVERT_IN 2
+#define OCM_EDT_INVERT_OUT 4
+#define OCM_EDT_NONE 0x7fffffff
+int ocm_edt_u8(ocm_ctx* ctx, const uint8_t* mask, int32_t H, int32_t W, int32_t flags, int64_t r2, int32_t* d2_out,
+               uint8_t* mask_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,7 @@ SIGNATURES = {
     "ocm_ks_select_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_i64,
                                   c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                   c_void_p]),
+    "ocm_edt_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64, c_void_p, c_void_p, c_void_p]),
     "ocm_colmean_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                      c_void_p]),
     "ocm_gram_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p,

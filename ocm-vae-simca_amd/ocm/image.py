@@ -11,6 +11,14 @@ include/ocm.h "images into objects") in place of nut_data.py:64-70
     res = model.predict_objects(objs.X, offsets=objs.offsets, rule="vote")
     decided = objs.paint_objects(res.pred[:, 0])
 
+Mask morphology (ocm_edt_u8; include/ocm.h "mask morphology") rests on the
+exact squared Euclidean distance transform d² of a mask: ``erode`` by the disc
+``disk(r)`` is d² > ⌊r²⌋, ``dilate`` the same on the complement, ``opening``
+and ``closing`` two of these, ``distance_transform`` the depth √d² itself, all
+equal to their scipy.ndimage counterparts bit for bit.  ``extract_objects(...,
+erode=2, fill_holes=True)`` drops the mixed rim of every object before its
+spectra are read and returns the depth of every kept pixel.
+
 ``objects_from_labels`` is host NumPy and needs no device.  The rest follows
 the estimator's rule: NumPy in, NumPy out; tensor in, device tensor out."""
 from __future__ import annotations
@@ -21,7 +29,7 @@ from dataclasses import dataclass
 import numpy as np
 
 __all__ = ["foreground_mask", "label", "objects_from_labels", "extract_objects", "gather_rows", "ObjectTable",
-           "LabelObjects"]
+           "LabelObjects", "disk", "distance_transform", "erode", "dilate", "opening", "closing", "fill_holes"]
 
 LabelObjects = namedtuple("LabelObjects", "order offsets n_pixels centroid bbox labels")
 
@@ -57,6 +65,33 @@ def _check_mask(mask, shape=None):
     if mask.shape[0] < 1 or mask.shape[1] < 1:
         raise ValueError(f"mask must have at least one pixel, got shape {tuple(mask.shape)}")
     return mask
+
+
+EDT_BORDER_BG, EDT_INVERT_IN, EDT_INVERT_OUT = 1, 2, 4  # include/ocm.h OCM_EDT_*
+EDT_NONE = 2**31 - 1  # d² without any background pixel
+EDT_MAX_SIDE = 32767  # H² + W² stays below 2³¹
+
+
+def _check_radius(radius, what="radius") -> int:
+    """⌊radius²⌋ of a real radius ≥ 0: the r2 that d² is compared with."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a real number >= 0, got {radius!r}") from None
+    if not (r >= 0.0) or r == float("inf"):  # NaN fails the comparison
+        raise ValueError(f"{what} must be a finite real number >= 0, got {radius!r}")
+    return int(np.floor(r * r))
+
+
+def _check_border(border) -> int:
+    if border not in ("ignore", "background"):
+        raise ValueError(f"border must be 'ignore' or 'background', got {border!r}")
+    return EDT_BORDER_BG if border == "background" else 0
+
+
+def _check_edt_shape(H, W, what):
+    if H > EDT_MAX_SIDE or W > EDT_MAX_SIDE:
+        raise ValueError(f"{what}: {H} x {W} exceeds {EDT_MAX_SIDE} pixels a side")
 
 
 # ---------------------------------------------------------------- host
@@ -111,6 +146,16 @@ def _host(a):
     if hasattr(a, "detach"):
         return a.detach().cpu().numpy()
     return np.asarray(a)
+
+
+def disk(radius):
+    """The bool (2⌊r⌋ + 1)² structuring element ``dx² + dy² ≤ ⌊r²⌋`` (host
+    NumPy): the disc that ``erode``, ``dilate``, ``opening`` and ``closing``
+    mean by ``radius``, for scipy.ndimage's ``structure=``."""
+    r2 = _check_radius(radius)
+    k = int(np.floor(float(radius)))
+    d = np.arange(-k, k + 1)
+    return d[:, None] ** 2 + d[None, :] ** 2 <= r2
 
 
 # ---------------------------------------------------------------- device
@@ -173,6 +218,115 @@ def _mask_u8(mask, device=None):
     if device is None:
         device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
     return (t.to(device) != 0).to(torch.uint8).contiguous().view(-1)
+
+
+def _edt_dev(mask_u8, H, W, flags, r2=0, want_d2=False, want_mask=False):
+    """One ocm_edt_u8 call on a (H·W,) uint8 device mask: (d2 int32 or None, mask_out uint8 or None)."""
+    import torch
+
+    from ._lib import Context, ptr, stream_handle
+
+    dev = mask_u8.device
+    d2 = torch.empty(H * W, dtype=torch.int32, device=dev) if want_d2 else None
+    out = torch.empty(H * W, dtype=torch.uint8, device=dev) if want_mask else None
+    _call("ocm_edt_u8", Context.get(dev.index).handle, ptr(mask_u8), H, W, flags, r2, ptr(d2), ptr(out),
+          stream_handle(dev))
+    return d2, out
+
+
+def _morph(mask, steps, what):
+    """``steps``: (flags, r2) per ocm_edt_u8 call, each on the mask the one before wrote."""
+    mask = _check_mask(mask)
+    H, W = (int(s) for s in mask.shape)
+    _check_edt_shape(H, W, what)
+    dev_in = _is_dev(mask)
+    m8 = _mask_u8(mask)
+    for flags, r2 in steps:
+        if r2 > 0:  # radius 0: the mask itself
+            m8 = _edt_dev(m8, H, W, flags, r2, want_mask=True)[1]
+    out = m8.view(H, W).bool()
+    return out if dev_in else out.cpu().numpy()
+
+
+def distance_transform(mask, border: str = "ignore", squared: bool = False):
+    """The exact Euclidean distance of every foreground pixel (non-zero) of an
+    (H, W) mask to the nearest background pixel, 0 on background (ocm_edt_u8).
+    ``border="ignore"``: only the image's own pixels count, which is
+    ``scipy.ndimage.distance_transform_edt(mask)`` whenever the mask has a
+    background pixel; ``"background"``: the pixels just outside the image are
+    background too (``distance_transform_edt(np.pad(mask, 1))[1:-1, 1:-1]``).
+    ``squared=True`` gives the int32 d² (``EDT_NONE`` = 2³¹ − 1 where there is no
+    background at all), else float64 √d² with ``inf`` there."""
+    flags = _check_border(border)
+    mask = _check_mask(mask)
+    H, W = (int(s) for s in mask.shape)
+    _check_edt_shape(H, W, "distance_transform")
+    dev_in = _is_dev(mask)
+    d2 = _edt_dev(_mask_u8(mask), H, W, flags, want_d2=True)[0].view(H, W)
+    out = d2 if squared else _depth(d2)
+    return out if dev_in else out.cpu().numpy()
+
+
+def _depth(d2):
+    import torch
+
+    return torch.where(d2 == EDT_NONE, torch.full((), float("inf"), dtype=torch.float64, device=d2.device),
+                       d2.double().sqrt())
+
+
+def erode(mask, radius, border: str = "background"):
+    """(H, W) bool erosion of a mask by ``disk(radius)``: d² > ⌊radius²⌋, one
+    ocm_edt_u8 call.  ``border="background"`` is ``scipy.ndimage.binary_erosion(
+    mask, disk(radius), border_value=0)``, ``"ignore"`` its ``border_value=1``."""
+    return _morph(mask, [(_check_border(border), _check_radius(radius))], "erode")
+
+
+def dilate(mask, radius):
+    """(H, W) bool dilation by ``disk(radius)``, the erosion of the complement:
+    ``scipy.ndimage.binary_dilation(mask, disk(radius))``."""
+    return _morph(mask, [(EDT_INVERT_IN | EDT_INVERT_OUT, _check_radius(radius))], "dilate")
+
+
+def opening(mask, radius):
+    """Erosion (border "background"), then dilation, two ocm_edt_u8 calls with
+    nothing between them: ``scipy.ndimage.binary_opening(mask, disk(radius))``."""
+    r2 = _check_radius(radius)
+    return _morph(mask, [(EDT_BORDER_BG, r2), (EDT_INVERT_IN | EDT_INVERT_OUT, r2)], "opening")
+
+
+def closing(mask, radius):
+    """Dilation, then erosion with border "ignore", so that the image edge does
+    not eat the result: ``binary_erosion(binary_dilation(mask, disc), disc,
+    border_value=1)`` with ``disc = disk(radius)``.  (``scipy.ndimage.
+    binary_closing`` erodes with border_value=0 and so clears the pixels within
+    ``radius`` of the edge.)"""
+    r2 = _check_radius(radius)
+    return _morph(mask, [(EDT_INVERT_IN | EDT_INVERT_OUT, r2), (0, r2)], "closing")
+
+
+def _fill_holes_dev(m8, H, W):
+    """(H·W,) uint8: the mask and its holes, the 4-connected components of the
+    complement whose label appears on no image edge."""
+    import torch
+
+    lab = _label_dev((m8 == 0).to(torch.uint8), H, W, 4)[0].view(H, W).long()
+    open_ = torch.zeros(H * W + 1, dtype=torch.bool, device=m8.device)  # labels ≤ H·W, whatever the image holds
+    open_[torch.cat([lab[0], lab[-1], lab[:, 0], lab[:, -1]])] = True
+    open_[0] = True  # label 0: the mask itself
+    return (m8.view(H, W).bool() | ~open_[lab]).to(torch.uint8).view(-1)
+
+
+def fill_holes(mask):
+    """(H, W) bool mask with its holes filled: ``scipy.ndimage.binary_fill_holes
+    (mask)``.  A hole is a 4-connected component of the complement that touches
+    no image edge (ocm_label_u8 on the complement)."""
+    mask = _check_mask(mask)
+    H, W = (int(s) for s in mask.shape)
+    if H * W > 2**31 - 1:
+        raise ValueError(f"fill_holes: {H} x {W} pixels exceed 2^31 - 1")
+    dev_in = _is_dev(mask)
+    out = _fill_holes_dev(_mask_u8(mask), H, W).view(H, W).bool()
+    return out if dev_in else out.cpu().numpy()
 
 
 def foreground_mask(cube, threshold: float = 1e-6, return_mean: bool = False):
@@ -242,7 +396,9 @@ class ObjectTable:
     ``pixel_index`` (n_fg,) int64 linear pixel index of every row of X;
     ``labels`` (H, W) int32, 0 background, 1..G; ``n_pixels`` (G,) int64;
     ``centroid`` (G, 2) float64 (row, column); ``bbox`` (G, 4) int64 r0, r1, c0,
-    c1; ``shape`` = (H, W).  NumPy arrays or device tensors, as the cube was."""
+    c1; ``shape`` = (H, W); ``depth`` (n_fg,) float64 distance of every row's pixel
+    to the background of the un-eroded mask, or None when it was not asked for.
+    NumPy arrays or device tensors, as the cube was."""
     X: object
     offsets: object
     pixel_index: object
@@ -251,6 +407,7 @@ class ObjectTable:
     centroid: object
     bbox: object
     shape: tuple
+    depth: object = None
 
     def _filled(self, count, values, fill, what):
         dev = _is_dev(self.labels)
@@ -296,7 +453,8 @@ class ObjectTable:
 
 
 def extract_objects(cube, mask=None, threshold: float = 1e-6, connectivity: int = 8,
-                    min_pixels: int = 1) -> ObjectTable:
+                    min_pixels: int = 1, erode: float = 0.0, fill_holes: bool = False,
+                    depth: bool = False) -> ObjectTable:
     """The objects of an (H, W, p) cube as an ``ObjectTable``: foreground mask
     (``foreground_mask`` unless ``mask`` is given), connected components
     (``label``), components of fewer than ``min_pixels`` pixels dropped and the
@@ -311,13 +469,27 @@ def extract_objects(cube, mask=None, threshold: float = 1e-6, connectivity: int 
     and ocm_segsum_f64 over the (n_fg, 2) pixel coordinates for the centroids
     (integer sums below 2⁵³: exact).  One small device-to-host read, the
     per-component pixel counts (n int64), sizes the outputs.  An image without
-    foreground gives G = 0, ``X`` of shape (0, p) and ``offsets`` = [0]."""
+    foreground gives G = 0, ``X`` of shape (0, p) and ``offsets`` = [0].
+
+    ``fill_holes`` fills the holes of the mask first (``fill_holes``).  ``erode``
+    > 0 then keeps, of every object of the un-eroded mask, the pixels deeper than
+    the disc: d² > ⌊erode²⌋ with the pixels outside the image as background
+    (``erode(mask, radius)``), under the label they already have, so an object
+    that erosion cuts through its neck stays one object; pixel counts, and with
+    them ``min_pixels``, are taken after erosion, so an object that vanishes is
+    dropped.  With ``erode`` > 0 or ``depth=True`` the table's ``depth`` holds √d²
+    of every kept pixel (one more ocm_edt_u8 call); with the defaults nothing
+    is added and ``depth`` is None."""
     connectivity = _check_connectivity(connectivity)
+    r2 = _check_radius(erode, "erode")
     cube, H, W, p = _check_cube(cube)
     if mask is not None:
         mask = _check_mask(mask, (H, W))
     if H * W > 2**31 - 1:
         raise ValueError(f"extract_objects: {H} x {W} pixels exceed 2^31 - 1")
+    want_depth = bool(depth) or float(erode) > 0  # a radius below 1 erodes nothing (r2 = 0) and still gives depth
+    if want_depth:
+        _check_edt_shape(H, W, "extract_objects(erode=, depth=)")
     import torch
 
     from . import engine
@@ -327,8 +499,15 @@ def extract_objects(cube, mask=None, threshold: float = 1e-6, connectivity: int 
     dev = X2.device
     HW = H * W
     m8 = _fgmask_dev(X2, ldx, threshold)[0] if mask is None else _mask_u8(mask, dev)
+    if fill_holes:
+        m8 = _fill_holes_dev(m8, H, W)
     lab, _ = _label_dev(m8, H, W, connectivity)
     lab64 = lab.long()
+    d2 = None
+    if want_depth:
+        d2, deep = _edt_dev(m8, H, W, EDT_BORDER_BG, r2, want_d2=True, want_mask=r2 > 0)
+        if r2 > 0:
+            lab64 = lab64 * deep
     counts = torch.bincount(lab64)[1:].cpu().numpy()  # the one read that sizes the outputs
     keep = counts >= max(int(min_pixels), 1)
     G = int(keep.sum())
@@ -359,6 +538,8 @@ def extract_objects(cube, mask=None, threshold: float = 1e-6, connectivity: int 
         centroid = torch.empty((0, 2), dtype=torch.float64, device=dev)
         bbox = torch.empty((0, 4), dtype=torch.int64, device=dev)
     fields = (X, off_d, pixel_index, labels, npx_d, centroid, bbox)
+    if want_depth:
+        fields += (d2[pixel_index].double().sqrt(),)
     if not dev_in:
         fields = tuple(f.cpu().numpy() for f in fields)
-    return ObjectTable(*fields, shape=(H, W))
+    return ObjectTable(*fields[:7], shape=(H, W), depth=fields[7] if want_depth else None)
