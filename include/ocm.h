@@ -1004,6 +1004,48 @@ int ocm_ks_select_f64(ocm_ctx* ctx, const double* Z, int64_t ldz, int64_t n, int
 int ocm_edt_u8(ocm_ctx* ctx, const uint8_t* mask, int32_t H, int32_t W, int32_t flags, int64_t r2, int32_t* d2_out,
                uint8_t* mask_out, void* stream);
 
+/* ---- robust calibration: the spatial median and sphered rows ----------------------------------------
+ * The L1 (spatial) median of the n rows x_i = X[rows ? rows[i] : i] minimises Σ_i ‖x_i − m‖.  It is found
+ * by Weiszfeld's iteration with the Vardi–Zhang correction for rows that coincide with the centre.  One
+ * step from the centre m, every difference, product and sum in fp64:
+ *   d_i = ‖x_i − m‖;  the η rows with d_i == 0 (exactly) take no part in the sums;
+ *   W = Σ 1/d_i,  S = Σ x_i/d_i  (p column sums),  T̃ = S/W,  R = S − W·m,  r = ‖R‖;
+ *   γ = 0 when η = 0, otherwise min(1, η/r) (1 when r = 0);
+ *   m⁺ = (1 − γ)·T̃ + γ·m  (m itself, bit for bit, when γ = 1);
+ *   stop when ‖m⁺ − m‖ ≤ tol·‖m⁺‖ or after max_iter steps.
+ *
+ * ocm_l1median_f32 / _f64: X [dev] with row pitch ldx ≥ p; rows [dev] n int64 row indices or NULL (rows
+ *   0..n − 1); center [dev] p doubles, in: the start, out: the result; dist_out [dev] n doubles or NULL:
+ *   the distances to the returned centre; info_out [dev] OCM_L1_INFO doubles: steps done, converged
+ *   (0 / 1), the last step's length ‖m⁺ − m‖, the objective Σ d_i and the number of coincident rows,
+ *   the last two at the returned centre.  max_iter = 0 evaluates the start.  Nothing is read back:
+ *   every step is queued at once and a step that finds the done flag raised returns at its first
+ *   instruction.  A step is k_l1_part, one workgroup per chunk of 256 rows at multiples of 256, which
+ *   writes the chunk's p + 3 partials (S, W, Σd, η) with the rows added in row order, then (more than
+ *   64 chunks) k_l1_group, which adds each aligned group of 64 chunks in chunk order, then k_l1_update,
+ *   one workgroup, which adds the groups in order and forms the update.  A row is used twice in a step,
+ *   for its distance and for the weighted sums: 16 rows at a time wait in LDS in between where
+ *   16·p·sizeof(element) ≤ 128 KiB (p ≤ 2048 float32, 1024 float64), and are read a second time, out of
+ *   L2, where p is wider.  One more pass measures the distances to the returned centre.  No atomics, no
+ *   fences, no workgroup waits for another: the result is a function of (X, rows, start, tol, max_iter)
+ *   alone, bit for bit.  16-byte loads where p, ldx and the base allow them, 8-byte or single-element
+ *   loads otherwise.  Workspace: (chunks + groups + 1)·(p + 3) + 8 doubles.  OCM_ERR_ARG for n < 1, n ≥ 2^31,
+ *   p < 1, ldx < p, tol < 0 (or NaN), max_iter < 0 or > 100000.  The row indices are not checked.
+ *
+ * ocm_sphere_rows_f32 / _f64: U[i·ldu + j] = (x_ij − center_j)/‖x_i − center‖ computed in fp64 and
+ *   rounded once to the element type; a row at distance 0 gives zeros.  dist_out [dev] n doubles or
+ *   NULL.  One wave per row; the row's second read comes out of the cache the first one filled.  U may
+ *   not overlap X. */
+#define OCM_L1_INFO 5
+int ocm_l1median_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                     double* center, double tol, int32_t max_iter, double* dist_out, double* info_out, void* stream);
+int ocm_l1median_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                     double* center, double tol, int32_t max_iter, double* dist_out, double* info_out, void* stream);
+int ocm_sphere_rows_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                        const double* center, float* U, int64_t ldu, double* dist_out, void* stream);
+int ocm_sphere_rows_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
+                        const double* center, double* U, int64_t ldu, double* dist_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

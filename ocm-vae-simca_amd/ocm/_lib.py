@@ -224,6 +224,14 @@ SIGNATURES = {
                                   c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                   c_void_p]),
     "ocm_edt_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64, c_void_p, c_void_p, c_void_p]),
+    "ocm_l1median_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_f64, c_i32, c_void_p,
+                                 c_void_p, c_void_p]),
+    "ocm_l1median_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_f64, c_i32, c_void_p,
+                                 c_void_p, c_void_p]),
+    "ocm_sphere_rows_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i64,
+                                    c_void_p, c_void_p]),
+    "ocm_sphere_rows_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i64,
+                                    c_void_p, c_void_p]),
     "ocm_colmean_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                      c_void_p]),
     "ocm_gram_f32_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p,

@@ -65,15 +65,18 @@ class _Spec:
         self.qlim = params.get("qlim", "jm")
         self.qcl = params.get("qcl", 0.95)
         self.dcl = params.get("dcl", 0.95)
-        if self.type == "dd":  # utils/SIMCA.py:42-48
-            self.t2lim = "chi2pom"
-            self.qlim = "chi2pom"
+        if self.type == "dd":  # utils/SIMCA.py:42-48; an explicit "chi2rob" stands
+            if self.t2lim != "chi2rob":
+                self.t2lim = "chi2pom"
+            if self.qlim != "chi2rob":
+                self.qlim = "chi2pom"
 
     def needs_train_stats(self) -> bool:
-        return self.t2lim in ("perc", "chi2pom") or self.qlim in ("perc", "chi2pom")
+        names = ("perc", "chi2pom", "chi2rob")
+        return self.t2lim in names or self.qlim in names
 
     def needs_percentile(self) -> bool:
-        return self.t2lim == "perc" or self.qlim == "perc"
+        return self.t2lim in ("perc", "chi2rob") or self.qlim in ("perc", "chi2rob")
 
 
 def _applicable(base_est, X, y, cv, lv_values, param_grid):

@@ -449,6 +449,69 @@ def segment_sums(X, offsets, checked: bool = False) -> torch.Tensor:
     return out
 
 
+L1_INFO = 5  # include/ocm.h OCM_L1_INFO: steps, converged, last step, objective, coincident rows
+
+
+def _robust_inputs(who: str, X, rows):
+    """(X read in place where its strides allow, ldx, rows on X's device, n) for
+    the ocm_l1median / ocm_sphere_rows entries.  A lazy ``PrepView`` is
+    materialised first (ocm_prep_apply_f32)."""
+    X = _plain(X)
+    if isinstance(X, PrepView):
+        X, rows = X.materialize(rows), None
+    if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and
+            X.dtype in (torch.float32, torch.float64)):
+        raise ValueError(f"{who}: X must be a 2-D float32 or float64 device tensor")
+    m, p = X.shape
+    if m < 1 or p < 1:
+        raise ValueError(f"{who}: X has shape {tuple(X.shape)}")
+    if (p > 1 and X.stride(1) != 1) or (m > 1 and X.stride(0) < p):
+        X = X.contiguous()
+    ldx = X.stride(0) if m > 1 else p
+    if rows is not None:
+        rows = rows.to(device=X.device, dtype=torch.int64).contiguous()
+        if rows.dim() != 1 or rows.numel() < 1:
+            raise ValueError(f"{who}: rows must be a non-empty 1-D index tensor")
+    return X, ldx, rows, (m if rows is None else int(rows.numel()))
+
+
+def l1_median(X, rows, start64: torch.Tensor, tol: float, max_iter: int, want_dist=True):
+    """The spatial median of the rows of X (ocm_l1median_f32 / _f64) from the
+    centre ``start64`` (p,) float64.  Returns (centre (p,) float64, info
+    (L1_INFO,) float64, distances (n,) float64 or None), device tensors: nothing
+    is read back, every step is queued at once."""
+    X, ldx, rows, n = _robust_inputs("l1_median", X, rows)
+    p = X.shape[1]
+    dev = X.device
+    center = start64.to(device=dev, dtype=torch.float64).clone().contiguous()
+    if tuple(center.shape) != (p,):
+        raise ValueError(f"l1_median: start has shape {tuple(center.shape)}, X has {p} columns")
+    info = torch.empty(L1_INFO, dtype=torch.float64, device=dev)
+    dist = torch.empty(n, dtype=torch.float64, device=dev) if want_dist else None
+    fn = "ocm_l1median_f64" if X.dtype == torch.float64 else "ocm_l1median_f32"
+    check(getattr(_lib.load(), fn)(Context.get(dev.index).handle, ptr(X), ldx, ptr(rows), n, p, ptr(center),
+                                   float(tol), int(max_iter), ptr(dist), ptr(info), _stream(dev)), fn)
+    return center, info, dist
+
+
+def sphere_rows(X, rows, center64: torch.Tensor, want_dist=False):
+    """U (n, p) in X's dtype, u_i = (x_i − centre)/‖x_i − centre‖ formed in fp64
+    (ocm_sphere_rows_f32 / _f64; zeros for a row on the centre), and the
+    distances (n,) float64 when asked for."""
+    X, ldx, rows, n = _robust_inputs("sphere_rows", X, rows)
+    p = X.shape[1]
+    dev = X.device
+    center = center64.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(center.shape) != (p,):
+        raise ValueError(f"sphere_rows: the centre has shape {tuple(center.shape)}, X has {p} columns")
+    U = torch.empty((n, p), dtype=X.dtype, device=dev)
+    dist = torch.empty(n, dtype=torch.float64, device=dev) if want_dist else None
+    fn = "ocm_sphere_rows_f64" if X.dtype == torch.float64 else "ocm_sphere_rows_f32"
+    check(getattr(_lib.load(), fn)(Context.get(dev.index).handle, ptr(X), ldx, ptr(rows), n, p, ptr(center), ptr(U),
+                                   p, ptr(dist), _stream(dev)), fn)
+    return U, dist
+
+
 def _ks_inputs(who: str, Z, w):
     """(Z read in place where its strides allow, ldz, w) for the ocm_ks_* entries."""
     if not (isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dim() == 2 and

@@ -4,6 +4,11 @@ device-side moments / percentiles / tail traces.
 Mirror of utils/SIMCA.py:156-236 (``_Tlim``, ``_Qlim``, ``_critic_distance``):
 same formulas, same quirks (chi2pom state kept on the estimator and
 overwritten per class; unknown limit names leave the result unbound).
+
+One limit name is this package's own: ``"chi2rob"``, chi2pom with the moment
+estimators replaced by their robust twins (``robust_dof``: the median and the
+interquartile range of the fit-set distances instead of their mean and
+variance), so that a few outlying calibration rows do not set the limits.
 """
 from __future__ import annotations
 
@@ -27,6 +32,43 @@ def _f_ppf(q: float, dfn: float, dfd: float) -> float:
 @functools.lru_cache(maxsize=4096)
 def _chi2_ppf(q: float, df: float) -> float:
     return stats.chi2.ppf(q, df)
+
+
+ROBUST_DOF_MAX = 250
+
+
+@functools.lru_cache(maxsize=1)
+def _robust_table():
+    """(median, IQR) of χ²(N) for N = 1..ROBUST_DOF_MAX."""
+    med = np.array([_chi2_ppf(0.5, float(N)) for N in range(1, ROBUST_DOF_MAX + 1)])
+    iqr = np.array([_chi2_ppf(0.75, float(N)) - _chi2_ppf(0.25, float(N)) for N in range(1, ROBUST_DOF_MAX + 1)])
+    return med, iqr
+
+
+def robust_ratio(N: int) -> float:
+    """IQR / median of χ²(N): strictly decreasing in N."""
+    med, iqr = _robust_table()
+    return float(iqr[N - 1] / med[N - 1])
+
+
+def robust_dof(M: float, S: float):
+    """The robust twin of Pomerantsev's moment estimators: (N, u0) of a
+    distance u ~ (u0/N)·χ²(N) from its median M and interquartile range S.  N is
+    the integer in 1..ROBUST_DOF_MAX whose χ²(N) has its IQR / median ratio
+    nearest S/M (ties to the lower N), and
+    u0 = ½·N·(M/median χ²(N) + S/IQR χ²(N))."""
+    M, S = float(M), float(S)
+    if not (M > 0.0 and S >= 0.0) or not (math.isfinite(M) and math.isfinite(S)):
+        raise ValueError(f"robust_dof: need a finite median > 0 and IQR >= 0, got median={M}, IQR={S}")
+    med, iqr = _robust_table()
+    N = int(np.argmin(np.abs(iqr / med - S / M))) + 1
+    u0 = 0.5 * N * (M / med[N - 1] + S / iqr[N - 1])
+    return N, float(u0)
+
+
+def _robust_params(u: "Moments"):
+    q1, M, q3 = u.percentile(25.0), u.percentile(50.0), u.percentile(75.0)
+    return robust_dof(M, q3 - q1)
 
 
 class Moments:
@@ -92,6 +134,11 @@ def t2_limit(est, T2: Moments, k: int) -> float:
         est._t2dof = Nh
         est._t2scfact = h0
         return h0 * _chi2_ppf(est.t2cl, Nh) / Nh
+    if est.t2lim == "chi2rob":
+        Nh, h0 = _robust_params(T2)
+        est._t2dof = Nh
+        est._t2scfact = h0
+        return float(h0 * _chi2_ppf(est.t2cl, Nh) / Nh)
     raise UnboundLocalError(f"local variable 'T2_limit' referenced before assignment (t2lim={est.t2lim!r})")
 
 
@@ -121,6 +168,11 @@ def q_limit(est, Q: Moments, thetas) -> float:
         Nv = max(round(2 * (v0 ** 2) / np.float64(Q.var(ddof=1))), 1)
         est._qdof = Nv
         est._qscfact = float(v0)
+        return float(v0 * _chi2_ppf(est.qcl, Nv) / Nv)
+    if est.qlim == "chi2rob":
+        Nv, v0 = _robust_params(Q)
+        est._qdof = Nv
+        est._qscfact = v0
         return float(v0 * _chi2_ppf(est.qcl, Nv) / Nv)
     raise UnboundLocalError(f"local variable 'Q_limit' referenced before assignment (qlim={est.qlim!r})")
 

@@ -228,10 +228,11 @@ class SIMCA(BaseEstimator, ClassifierMixin):
             self.n_components = [self.n_components[0]] * len(self.model_class)
         elif len(self.n_components) != len(self.model_class):
             raise ValueError("n_components length must match number of classes")
-        if self.type == "dd" and self.t2lim != "chi2pom":
+        # dd needs data-driven limits: an explicit "chi2rob" (limits.robust_dof) stands
+        if self.type == "dd" and self.t2lim not in ("chi2pom", "chi2rob"):
             print("t2lim set as chi2pom")
             self.t2lim = "chi2pom"
-        if self.type == "dd" and self.qlim != "chi2pom":
+        if self.type == "dd" and self.qlim not in ("chi2pom", "chi2rob"):
             print("qlim set as chi2pom")
             self.qlim = "chi2pom"
 
