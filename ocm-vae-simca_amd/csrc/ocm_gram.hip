@@ -2084,9 +2084,11 @@ __global__ __launch_bounds__(256, 1) void k_gram8w(Q8Plan q, SegTable st, int nt
 
 // ---------------------------------------------------------------------------
 // k_gram8e — k_gram8w<ALIGNED, SYNC = 2> as a persistent kernel: one workgroup
-// per CU walks its share of the (chunk, tile) items (ocm_gram_map.h: static
-// striding inside each XCD's contiguous range, in the order the one-item
-// launch dispatched them; no counter, nothing to reset, capture-safe).  What
+// per CU walks its share of the (chunk, tile) items (ocm_gram_map.h, `map`:
+// MAP_RANGE, static striding inside each XCD's contiguous range, in the order
+// the one-item launch dispatched them, or MAP_ROUND, rounds of gridDim.x
+// consecutive items that all XCDs sweep together; either way from blockIdx
+// alone: no counter, nothing to reset, capture-safe).  What
 // a workgroup used to pay around its stage loop now runs beside MFMAs:
 //   * the band walk is done once per workgroup into an LDS table;
 //   * the 24 load slots of an item's last stage (clamped duplicates in
@@ -2105,10 +2107,15 @@ __global__ __launch_bounds__(256, 1) void k_gram8w(Q8Plan q, SegTable st, int nt
 // SKIP (θ3 trace Gram, 136 items: one per workgroup on this chip): no
 // cross-item prefetch, an item's stage 0 is loaded at its start.
 // ---------------------------------------------------------------------------
+// cache-policy bits of the partials' stores (A/B builds: 2 = non-temporal)
+#ifndef OCM_G8E_STORE_AUX
+#define OCM_G8E_STORE_AUX 0
+#endif
 constexpr int G8P_TMAP = 2048;  // off-diagonal tiles in the LDS table (nt ≤ 64); more: walk per item
 template <bool SKIP>
 __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
-                                                   int nwg, int nblocks, float* __restrict__ part, int chunk0) {
+                                                   int nwg, int nblocks, float* __restrict__ part, int chunk0,
+                                                   int map) {
   __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];      // wave-private: row, column scales
   __shared__ __attribute__((aligned(16))) float runl[4][16][64][4];  // wave-private f32 running sums
   __shared__ uint16_t tmap[G8P_TMAP];                                // off-diagonal rank → ti << 8 | tj
@@ -2123,7 +2130,8 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
     }
     __syncthreads();
   }
-  const ocm_g8::Slot sl = ocm_g8::slot_of(total_wg, (int)gridDim.x, (int)blockIdx.x);
+  // the work map (ocm_g8::Map), chosen once: uniform over the launch
+  const ocm_g8::Slot sl = ocm_g8::map_slot(map, total_wg, (int)gridDim.x, (int)blockIdx.x);
   if (sl.count == 0) return;  // workgroup-uniform
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2226,7 +2234,7 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)pv[e]), ro, vout,
-                                            ((a * 16 + e) * Q8T + c * 16) * 4, 0);
+                                            ((a * 16 + e) * Q8T + c * 16) * 4, OCM_G8E_STORE_AUX);
   };
   // one stage: 96 MFMAs on (CA, CB), sub-blocks row-major, six products each;
   // the 24 loads at scalar offset `so` behind (da, db) into (NA, NB), one per
@@ -2988,7 +2996,7 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   // barriers, r03s), as a persistent kernel (k_gram8e, one workgroup per CU).
   // The product library launches only that variant; the A/B selectors
   // (OCM_GRAM8_ORDER = wg | packed | aligned | sync1 | front | sync4 | sync3,
-  // OCM_GRAM8_XCD, OCM_GRAM8_PIECES, OCM_Q8_CG) exist only in `make exp`
+  // OCM_GRAM8_XCD, OCM_GRAM8_MAP, OCM_GRAM8_PIECES, OCM_Q8_CG) exist only in `make exp`
   // builds (OCM_EXP_SELECTORS), which the product never loads.  wg: the same
   // order with one item per workgroup (k_gram8w), the launch before k_gram8e.
   int order = 3;
@@ -2996,7 +3004,10 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   (void)no_remap;
   int pieces = 1;
   int qcg = 1;  // column groups per quantiser workgroup
+  // k_gram8e's work map (ocm_gram_map.h); OCM_GRAM8_MAP = range | round in exp builds
+  int gmap = ocm_g8::MAP_ROUND;
 #ifdef OCM_EXP_SELECTORS
+  if (const char* mv = getenv("OCM_GRAM8_MAP")) gmap = !strcmp(mv, "round") ? ocm_g8::MAP_ROUND : ocm_g8::MAP_RANGE;
   const char* ord = getenv("OCM_GRAM8_ORDER");
   if (ord && !strcmp(ord, "wg")) order = 9;
   if (ord && !strcmp(ord, "packed")) order = 0;
@@ -3092,10 +3103,10 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     const unsigned pgrid = (unsigned)std::min<int64_t>(total, std::max(ctx->num_cus, ocm_g8::NXCD));
     if (tr_O && !k32 && order == 3)
       hipLaunchKernelGGL(k_gram8e<true>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
-                         nblocks, pg, (int)c0);
+                         nblocks, pg, (int)c0, gmap);
     else if (!k32 && order == 3)
       hipLaunchKernelGGL(k_gram8e<false>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
-                         nblocks, pg, (int)c0);
+                         nblocks, pg, (int)c0, gmap);
 #ifdef OCM_EXP_SELECTORS
     else if (tr_O && !k32 && order == 9)
       hipLaunchKernelGGL((k_gram8w<true, 2, false, true>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt,

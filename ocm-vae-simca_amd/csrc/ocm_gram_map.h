@@ -8,7 +8,8 @@
 // first the off-diagonal 128×128 tiles in band order, four blocks each, then
 // the nt diagonal tiles, three blocks each (the strictly-lower block of a
 // diagonal tile is its mirror), packed.  Logical item ids run chunk-major;
-// XCD x (workgroups b with b % 8 == x) owns a contiguous range of them.
+// XCD x (workgroups b with b % 8 == x) owns a contiguous range of them
+// (slot_of), or of every round of `grid` consecutive ones (round_slot).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -58,6 +59,27 @@ OCM_MAP_HD Slot slot_of(int total, int grid, int b) {
   r.step = S;
   r.count = s < n ? (n - s + S - 1) / S : 0;
   return r;
+}
+
+// round sweep (grid ≤ total): the launch runs in rounds, round r being the
+// logical items [r·grid, (r + 1)·grid) ∩ [0, total); inside a round XCD x
+// takes the contiguous range xcd_first(grid, x) … of it, slot by slot, so an
+// XCD's workgroups are on band-consecutive items as under slot_of, but all
+// eight XCDs advance through the chunk list together: a round spans at most
+// ⌈grid / nwg⌉ + 1 chunks.  For total ≤ grid (one item or none per
+// workgroup) it is slot_of's map.  From blockIdx alone, like slot_of.
+OCM_MAP_HD Slot round_slot(int total, int grid, int b) {
+  Slot r;
+  r.first = xcd_first(grid, b % NXCD) + b / NXCD;
+  r.step = grid;
+  r.count = r.first < total ? (total - r.first - 1) / grid + 1 : 0;
+  return r;
+}
+
+// the two maps of the persistent launch, as k_gram8e's launch argument
+enum Map { MAP_RANGE = 0, MAP_ROUND = 1 };
+OCM_MAP_HD Slot map_slot(int map, int total, int grid, int b) {
+  return map == MAP_ROUND ? round_slot(total, grid, b) : slot_of(total, grid, b);
 }
 
 // off-diagonal tile of band-order rank `rank` (0 .. nt(nt−1)/2 − 1)

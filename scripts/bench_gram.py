@@ -9,7 +9,9 @@ of each mode against an fp64 Gram of a row sample.
 A third field sets OCM_GRAM8_ORDER for that variant (k_gram8e block order),
 a fourth OCM_GRAM8_PIECES (quantiser / Gram overlap), a fifth OCM_Q8_CG
 (column groups per quantiser row block on consecutive workgroups), a sixth
-OCM_GRAM8_XCD (0: no XCD remap of the Gram workgroups).  "wall" is the whole
+OCM_GRAM8_XCD (0: no XCD remap of the Gram workgroups), a seventh
+OCM_GRAM8_MAP (range | round: k_gram8e's work map).  The selectors are read by
+`make exp` libraries only (OCM_LIB=…, OCM_ALLOW_EXP_LIB=1).  "wall" is the whole
 call (guard, quantiser, Gram, reduce) between two device synchronisations.
 """
 import argparse
@@ -48,17 +50,17 @@ def main():
     ctx = Context.get(0)
     import time
 
-    variants = [tuple(v.split(":")[:2]) + tuple((v.split(":") + ["", "", "", ""])[2:6]) for v in args.variants.split(",")]
-    variants = [(m, int(c), o, pc, cg, xr) for m, c, o, pc, cg, xr in variants]
+    variants = [tuple(v.split(":")[:2]) + tuple((v.split(":") + ["", "", "", "", ""])[2:7]) for v in args.variants.split(",")]
+    variants = [(m, int(c), o, pc, cg, xr, mp) for m, c, o, pc, cg, xr, mp in variants]
     res = {":".join(map(str, v)): [] for v in variants}
     wall = {k: [] for k in res}
     quant = {k: [] for k in res}
     flop = args.rows * args.p * (args.p + 1)
     for _ in range(args.rounds):
-        for mode, chunk, order, pcs, qcg, xr in variants:
-            key = ":".join(map(str, (mode, chunk, order, pcs, qcg, xr)))
+        for mode, chunk, order, pcs, qcg, xr, gmap in variants:
+            key = ":".join(map(str, (mode, chunk, order, pcs, qcg, xr, gmap)))
             for var, val in (("OCM_GRAM8_ORDER", order), ("OCM_GRAM8_PIECES", pcs), ("OCM_Q8_CG", qcg),
-                             ("OCM_GRAM8_XCD", xr)):
+                             ("OCM_GRAM8_XCD", xr), ("OCM_GRAM8_MAP", gmap)):
                 if val:
                     os.environ[var] = val
                 else:
@@ -86,6 +88,7 @@ def main():
     os.environ.pop("OCM_GRAM8_PIECES", None)
     os.environ.pop("OCM_Q8_CG", None)
     os.environ.pop("OCM_GRAM8_XCD", None)
+    os.environ.pop("OCM_GRAM8_MAP", None)
     for mode in sorted({v[0] for v in variants}):
         Gm, _ = engine.gram(X, None, [0, ns], shift, mode=mode)
         err = ((Gm[0] - Gref).abs().max() / Gref.abs().max()).item()
@@ -93,7 +96,7 @@ def main():
     for key, vals in res.items():
         w = sorted(wall[key])
         qq = sorted(quant[key])
-        print(f"{key:18s} TFLOP/s median {sorted(vals)[len(vals) // 2]:7.2f}  all {[round(v, 1) for v in vals]}  "
+        print(f"{key:24s} TFLOP/s median {sorted(vals)[len(vals) // 2]:7.2f}  all {[round(v, 1) for v in vals]}  "
               f"wall ms median {w[len(w) // 2]:7.3f}  quantise ms median {qq[len(qq) // 2]:6.3f}", flush=True)
 
 
