@@ -769,7 +769,7 @@ __device__ __forceinline__ int q8_qslot(int P) { return P ^ ((P >> 3) & 7); }
 // 4cq .. 4cq+3: a wave instruction reads 8 rows × 128 B) and row slice
 // rs = t >> 3 (rows 16rs .. 16rs+15 = half rs&1 of 32-row group rs>>1), so
 // each (column, digit) of a thread is one 16-B piece of the digit image.  The
-// pieces are staged through LDS (one digit plane, 24 KiB, at a time) so that
+// pieces are staged through LDS (the three digit planes, 48 KiB each) so that
 // the stores leave as contiguous 1-KiB runs (one 32-row group × 32 columns).
 constexpr int Q8QC = 32;                   // columns per quantiser workgroup
 constexpr int Q8QS = Q8BLK / 16;           // 16-row slices per block (96)
@@ -778,38 +778,30 @@ constexpr int Q8QT = Q8QS * (Q8QC / 4);    // threads (768)
 // y − shift.  Column sums, the outlier screen, the block scale, the digits
 // and their LDS-staged stores (shared by k_q8_quant and k_q8_quant_prep).
 // q8_tail's LDS (the caller declares it: k_q8_quant_prep overlays its own
-// load-phase buffers on it)
-// digit planes staged in LDS at once: 3 (one barrier, 147 KiB with the
-// reduction buffers overlaid — the quantiser is one workgroup per CU by its
-// registers anyway) or 1 (a barrier pair per plane); 3.02 vs 3.04 and 2.62 vs
-// 2.69 ms on two boxes, identical digits (profiles/r05zc_quant_stage_ab.json)
-#ifdef OCM_Q8_STAGE1
-constexpr int Q8NST = 1;
-#else
-constexpr int Q8NST = 3;
-#endif
-template <int QC = Q8QC>
-struct Q8TailLdsT {
+// load-phase buffers on it).  All three digit planes are staged at once (one
+// barrier, 147 KiB with the reduction buffers overlaid — the quantiser is one
+// workgroup per CU by its registers anyway).  One plane at a time, a barrier
+// pair per plane, measured equal: 3.02 vs 3.04 and 2.62 vs 2.69 ms on two
+// boxes, identical digits (profiles/r05zc_quant_stage_ab.json).
+struct Q8TailLds {
   union {  // the reduction buffers are dead once the block scales are known
     struct {
-      __attribute__((aligned(16))) float wmax[Q8QS][QC];
-      __attribute__((aligned(16))) double wsum[Q8QS][QC];
-      float pmax[8][QC];
-      double psum[8][QC];
+      __attribute__((aligned(16))) float wmax[Q8QS][Q8QC];
+      __attribute__((aligned(16))) double wsum[Q8QS][Q8QC];
+      float pmax[8][Q8QC];
+      double psum[8][Q8QC];
     } r;
-    __attribute__((aligned(16))) char stage[Q8NST * Q8SPB * QC * 32];  // digit planes: 48 KiB each at QC = 32
+    __attribute__((aligned(16))) char stage[3 * Q8SPB * Q8QC * 32];  // digit planes: 48 KiB each
   } u;
-  __attribute__((aligned(16))) float fmax_[QC];
+  __attribute__((aligned(16))) float fmax_[Q8QC];
 };
-using Q8TailLds = Q8TailLdsT<>;
-template <int QC = Q8QC>
 // th: the thresholds of the thread's four columns, loaded by the caller in
 // its load phase (a global load here would wait, through vmcnt, for every
 // store the caller has issued — the write-through X′ rows)
 __device__ __forceinline__ void q8_tail(f32x4 (&v)[16], int tid, int cq, int rs, int cg0, int c0, int64_t rb,
                                         const Q8Plan& q, int chunk, int b, const SegTable& st,
-                                        double* __restrict__ colblk, Q8TailLdsT<QC>& L, const f32x4 th) {
-  constexpr int NT = Q8QS * (QC / 4);  // threads
+                                        double* __restrict__ colblk, Q8TailLds& L, const f32x4 th) {
+  constexpr int QC = Q8QC, NT = Q8QT;
   char* stage = L.u.stage;
   auto& wmax = L.u.r.wmax;
   auto& wsum = L.u.r.wsum;
@@ -958,56 +950,36 @@ __device__ __forceinline__ void q8_tail(f32x4 (&v)[16], int tid, int cq, int rs,
   constexpr int GIMG = QC * 32;  // bytes per group image
   char* gdst = q.digits + ((size_t)chunk * (st.chunk_rows / Q8K) + (size_t)b * Q8SPB) * q.P8 * 32 + (size_t)cg0 * 32;
   const int grp = rs >> 1, half = rs & 1;
-  if constexpr (Q8NST == 3) {
 #pragma unroll
-    for (int dg = 0; dg < 3; ++dg)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        *reinterpret_cast<i32x4*>(&stage[dg * Q8SPB * GIMG + grp * GIMG + q8_qslot(2 * (4 * cq + e) + half) * 16]) =
-            w[dg][e];
-    __syncthreads();
-#pragma unroll
-    for (int dg = 0; dg < 3; ++dg)
-#pragma unroll
-      for (int k = 0; k < Q8SPB * GIMG / (16 * NT); ++k) {
-        const int o = 16 * (tid + NT * k);
-        const int g = o / GIMG, within = o - g * GIMG;
-        *reinterpret_cast<i32x4*>(gdst + (size_t)dg * q.plane + (size_t)g * q.P8 * 32 + within) =
-            *reinterpret_cast<const i32x4*>(&stage[dg * Q8SPB * GIMG + g * GIMG + q8_qslot(within >> 4) * 16]);
-      }
-    return;
-  }
-#pragma unroll
-  for (int dg = 0; dg < 3; ++dg) {
+  for (int dg = 0; dg < 3; ++dg)
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      *reinterpret_cast<i32x4*>(&stage[grp * GIMG + q8_qslot(2 * (4 * cq + e) + half) * 16]) = w[dg][e];
-    __syncthreads();
-    static_assert(Q8SPB * GIMG % (16 * NT) == 0, "copy-out passes");
+      *reinterpret_cast<i32x4*>(&stage[dg * Q8SPB * GIMG + grp * GIMG + q8_qslot(2 * (4 * cq + e) + half) * 16]) =
+          w[dg][e];
+  __syncthreads();
+  static_assert(Q8SPB * GIMG % (16 * NT) == 0, "copy-out passes");
+#pragma unroll
+  for (int dg = 0; dg < 3; ++dg)
 #pragma unroll
     for (int k = 0; k < Q8SPB * GIMG / (16 * NT); ++k) {
-      const int o = 16 * (tid + NT * k);  // byte offset in the stage image
+      const int o = 16 * (tid + NT * k);  // byte offset in the plane's stage image
       const int g = o / GIMG, within = o - g * GIMG;
       *reinterpret_cast<i32x4*>(gdst + (size_t)dg * q.plane + (size_t)g * q.P8 * 32 + within) =
-          *reinterpret_cast<const i32x4*>(&stage[g * GIMG + q8_qslot(within >> 4) * 16]);
+          *reinterpret_cast<const i32x4*>(&stage[dg * Q8SPB * GIMG + g * GIMG + q8_qslot(within >> 4) * 16]);
     }
-    __syncthreads();
-  }
 }
 
-// QC: columns per workgroup.  16-column workgroups (384 threads, two per CU)
-// measured 4.25 against 3.02 ms for the default at 1M × 2048: rows read as
-// 16 × 64 B per wave instruction lose more than the second workgroup per CU
-// gains (profiles/r05j_quant_qc16_ab.json)
-template <bool GATHER, int CG = 1, int QC = Q8QC>
-__global__ __launch_bounds__(Q8QS * (QC / 4), 1) void k_q8_quant(const float* __restrict__ X, int64_t ldx,
-                                                                 const int64_t* __restrict__ rows, int p,
-                                                                 const float* __restrict__ shift, SegTable st,
-                                                                 Q8Plan q, double* __restrict__ colblk, int cb0) {
-  // CG > 1 (A/B): CG neighbouring 32-column groups of one row block on
-  // consecutive workgroups (they run at the same time on other CUs), so each
-  // row's CG·128 bytes are read close in time
-  const int gbk = (int)(blockIdx.x / CG) + cb0;  // (chunk, block) of the call's chunk range
+// Q8QC = 32 columns per workgroup.  16-column workgroups (384 threads, two
+// per CU) measured 4.25 against 3.02 ms for the default at 1M × 2048: rows
+// read as 16 × 64 B per wave instruction lose more than the second workgroup
+// per CU gains (profiles/r05j_quant_qc16_ab.json)
+template <bool GATHER>
+__global__ __launch_bounds__(Q8QT, 1) void k_q8_quant(const float* __restrict__ X, int64_t ldx,
+                                                      const int64_t* __restrict__ rows, int p,
+                                                      const float* __restrict__ shift, SegTable st, Q8Plan q,
+                                                      double* __restrict__ colblk, int cb0) {
+  constexpr int QC = Q8QC;
+  const int gbk = (int)blockIdx.x + cb0;  // (chunk, block) of the call's chunk range
   const int chunk = gbk / q.nblk, b = gbk - chunk * q.nblk;
   const int tid = threadIdx.x;
   const int cq = tid % (QC / 4), rs = tid / (QC / 4);
@@ -1018,8 +990,8 @@ __global__ __launch_bounds__(Q8QS * (QC / 4), 1) void k_q8_quant(const float* __
   // blocks past the chunk's rows are written too (zero digits, scale 1): the
   // Gram kernels read whole blocks
   const int64_t rb = r0 + (int64_t)b * Q8BLK + 16 * rs;
-  const int cg0 = (int)(blockIdx.y * CG + blockIdx.x % CG) * QC;  // first column of the workgroup
-  const int c0 = cg0 + 4 * cq;                                    // first of this thread's 4 columns
+  const int cg0 = (int)blockIdx.y * QC;  // first column of the workgroup
+  const int c0 = cg0 + 4 * cq;           // first of this thread's 4 columns
   const bool vec = (ldx % 4 == 0) && (c0 + 3 < p) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
   f32x4 sh;  // shift == nullptr: a zero shift (internal Grams)
 #pragma unroll
@@ -1061,10 +1033,10 @@ __global__ __launch_bounds__(Q8QS * (QC / 4), 1) void k_q8_quant(const float* __
       for (int e = 0; e < 4; ++e) v[j][e] = (g < r1 && c0 + e < p) ? x[e] - sh[e] : 0.f;
     }
   }
-  __shared__ Q8TailLdsT<QC> lds;
+  __shared__ Q8TailLds lds;
   const float inf = __builtin_inff();  // q.thr == nullptr: no screen (internal Grams)
-  q8_tail<QC>(v, tid, cq, rs, cg0, c0, rb, q, chunk, b, st, colblk, lds,
-              q.thr ? *reinterpret_cast<const f32x4*>(q.thr + c0) : f32x4{inf, inf, inf, inf});
+  q8_tail(v, tid, cq, rs, cg0, c0, rb, q, chunk, b, st, colblk, lds,
+          q.thr ? *reinterpret_cast<const f32x4*>(q.thr + c0) : f32x4{inf, inf, inf, inf});
 }
 
 // k_q8_quant with the preprocessing of a lazy view applied in the load path
@@ -1079,19 +1051,6 @@ __global__ __launch_bounds__(Q8QS * (QC / 4), 1) void k_q8_quant(const float* __
 // (4 + 2·4HQ)-column window back from the image or the halo table; the row
 // ends use the least-squares edge rows.  The load phase's LDS overlays
 // q8_tail's.
-#ifdef OCM_QP_DPP
-// the quad of the lane CTRL's DPP row shift names (row_shr / row_shl inside 16 lanes)
-// (old = 0, not the source: with old == src hipcc (ROCm 7.2) folded the four
-// components' DPP moves into one and copied its result to all four)
-template <int CTRL>
-__device__ __forceinline__ float q8_dpp1(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ f32x4 q8_dpp4(f32x4 x) {
-  return f32x4{q8_dpp1<CTRL>(x.x), q8_dpp1<CTRL>(x.y), q8_dpp1<CTRL>(x.z), q8_dpp1<CTRL>(x.w)};
-}
-#endif
 template <int HH>
 struct Q8PrepLds {
   static constexpr int HQ = (HH + 3) / 4, WN = 2 * HH + 1;
@@ -1234,37 +1193,6 @@ __global__ __launch_bounds__(Q8QT, 1) void k_q8_quant_prep(const float* __restri
     const float srj = __shfl(srl[j & 1], j >> 1, 8);
     const f32x4* hrow = L.halo + (rs * 16 + j) * 2 * HQ;  // this row's halo: [side][quad]
     float win[4 + 2 * 4 * HQ];  // columns c0 − 4HQ .. c0 + 3 + 4HQ
-#ifdef OCM_QP_DPP
-    // (make exp A/B; measured: the same digits and X′ bit for
-    // bit, and no faster — cheese write-through quantiser 5.95–5.98 against
-    // 5.86–5.95 ms, profiles/r06k_qp_dpp_ab.txt: the LDS row image is not what
-    // holds the fused quantiser back; its VALU work (3310 instructions, the
-    // taps already on packed f32) and the extra X′ write stream are)
-    // the neighbouring quads of the slice by DPP lane shifts
-    // (row_shr / row_shl by s lanes inside the 16-lane DPP row: lanes whose
-    // source falls outside their own eight-lane slice take the halo instead),
-    // the out-of-slice quads from the halo table, which the load phase filled:
-    // nothing waits on this row's own LDS store; the row image only where the
-    // grid's edge workgroups read it (the least-squares edge rows)
-    if (edge_wg) *reinterpret_cast<f32x4*>(row_img + 4 * cq) = xs;
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) win[4 * HQ + e] = xs[e];
-#pragma unroll
-    for (int sft = 1; sft <= HQ; ++sft) {
-      static_assert(HQ <= 2, "DPP shifts of one or two lanes");
-      f32x4 l4 = sft == 1 ? q8_dpp4<0x111>(xs) : q8_dpp4<0x112>(xs);  // row_shr: quad cq − sft
-      f32x4 r4 = sft == 1 ? q8_dpp4<0x101>(xs) : q8_dpp4<0x102>(xs);  // row_shl: quad cq + sft
-      const int ql = cq - sft, qr = cq + sft;
-      if (ql < 0) l4 = hrow[HQ + ql];
-      if (qr >= Q8QC / 4) r4 = hrow[HQ + (qr - Q8QC / 4)];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        win[4 * (HQ - sft) + e] = l4[e];
-        win[4 * (HQ + sft) + e] = r4[e];
-      }
-    }
-#else
     // the lanes of one row slice exchange their quads through the row image
     // (wave-private: LDS instructions of a wave execute in order)
     *reinterpret_cast<f32x4*>(row_img + 4 * cq) = xs;
@@ -1279,7 +1207,6 @@ __global__ __launch_bounds__(Q8QT, 1) void k_q8_quant_prep(const float* __restri
 #pragma unroll
       for (int e = 0; e < 4; ++e) win[4 * k + e] = t4[e];
     }
-#endif
     f32x4 y;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -1608,18 +1535,13 @@ __global__ __launch_bounds__(256) void k_gram_fixup(const float* __restrict__ X,
 // One wave per SIMD, 64×64 per wave; the scale-block flush goes through
 // wave-private LDS.
 // ---------------------------------------------------------------------------
-// band shape of the Gram's tile order (tile rows × tile columns); make exp
-// builds override it for A/B
-// (the defaults, 4 × 8, are in ocm_gram_map.h)
-constexpr int G8_BAND_R = ocm_g8::BAND_R, G8_BAND_C = ocm_g8::BAND_C;
 __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
                                                    int nwg, int nblocks, float* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];        // wave-private: row, column scales
   __shared__ __attribute__((aligned(16))) float runl[4][4][4][64][4];  // wave-private f32 running sums
 
-  const int b = blockIdx.x;
-  const int q8 = total_wg / 8, r8 = total_wg % 8, x8 = b % 8;
-  const int wg = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+  // XCD-aware remap: each XCD a contiguous range of logical items (chunk-major)
+  const int wg = ocm_g8::logical_item(total_wg, blockIdx.x);
   const int chunk = wg / nwg;
   // 64×64 blocks packed four per workgroup: the upper triangle of 128×128
   // tiles has 4·ntiles − nt valid blocks (a diagonal tile's strictly-lower
@@ -1633,14 +1555,18 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
   // triangle), so the ≈ 32 tiles an XCD runs at once share 12 panels rather
   // than one row panel and 32 column panels: 15 % fewer bytes fetched beyond
   // L2 and 1.5–2 % faster than the row-major triangle order (r02_band).  The
-  // walk is wave-uniform scalar work, ≤ ntiles steps at kernel start.
+  // walk is wave-uniform scalar work, ≤ ntiles steps at kernel start; the
+  // band shape (4 × 8) is ocm_gram_map.h's.  It is ocm_g8::packed_block written
+  // out: the call compiled to four more scalar instructions ahead of the stage
+  // loop and measured 10.84–10.85 against 10.73–10.83 ms (medians of two
+  // alternating sets), so the walk stays inline.
   int ti = -1, tj = 0, wm = 0, wn = 0;
   {
     int rem = bi;
-    for (int u = 0; u < nt && ti < 0; u += G8_BAND_R)
-      for (int v = u; v < nt && ti < 0; v += G8_BAND_C)
-        for (int a = u; a < min(nt, u + G8_BAND_R) && ti < 0; ++a)
-          for (int c = max(v, a); c < min(nt, v + G8_BAND_C); ++c) {
+    for (int u = 0; u < nt && ti < 0; u += ocm_g8::BAND_R)
+      for (int v = u; v < nt && ti < 0; v += ocm_g8::BAND_C)
+        for (int a = u; a < min(nt, u + ocm_g8::BAND_R) && ti < 0; ++a)
+          for (int c = max(v, a); c < min(nt, v + ocm_g8::BAND_C); ++c) {
             const int nbk = (a == c) ? 3 : 4;
             if (rem < nbk) {
               ti = a;
@@ -1681,32 +1607,15 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
   const float* srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I + wm * 64 + lane;
   const float* scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J + wn * 64 + lane;
 
-#define Q8D_LOAD_B(FB, x_, dg_, so_) \
-  FB[x_][dg_] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rb[dg_], voff + x_ * 1024, so_, 0)
 #define Q8D_LOAD(FA, FB, STG)                                                                         \
   do {                                                                                              \
     const int so_ = (STG) * (int)gstride;                                                           \
     _Pragma("unroll") for (int x_ = 0; x_ < 2; ++x_)                                                \
     _Pragma("unroll") for (int dg_ = 0; dg_ < 3; ++dg_) {                                           \
       FA[x_][dg_] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ra[dg_], voff + x_ * 1024, so_, 0); \
-      Q8D_LOAD_B(FB, x_, dg_, so_);                                                                 \
+      FB[x_][dg_] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rb[dg_], voff + x_ * 1024, so_, 0); \
     }                                                                                               \
   } while (0)
-// Z: first stage of a scale block — each accumulator's first product starts
-// from an inline zero (no separate reset after the flush)
-#define Q8D_MFMA(FA, FB, Z)                                                                           \
-  do {                                                                                              \
-    _Pragma("unroll") for (int a_ = 0; a_ < 2; ++a_)                                                \
-    _Pragma("unroll") for (int c_ = 0; c_ < 2; ++c_) {                                              \
-      acc1[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][0], FB[c_][0], (Z) ? i32x16{} : acc1[a_][c_], 0, 0, 0); \
-      acc2[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][0], FB[c_][1], (Z) ? i32x16{} : acc2[a_][c_], 0, 0, 0); \
-      acc2[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][1], FB[c_][0], acc2[a_][c_], 0, 0, 0); \
-      acc3[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][0], FB[c_][2], (Z) ? i32x16{} : acc3[a_][c_], 0, 0, 0); \
-      acc3[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][2], FB[c_][0], acc3[a_][c_], 0, 0, 0); \
-      acc3[a_][c_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[a_][1], FB[c_][1], acc3[a_][c_], 0, 0, 0); \
-    }                                                                                               \
-  } while (0)
-
   i32x16 acc1[2][2], acc2[2][2], acc3[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -1747,30 +1656,11 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
       }
     }
   };
-// stage STG computes on set CUR; the loads of stage STG+2 fill set NXT first
-#define Q8D_S0 F0A, F0B, F2A, F2B
-#define Q8D_S1 F1A, F1B, F0A, F0B
-#define Q8D_S2 F2A, F2B, F1A, F1B
-// diagnostic builds only (make exp; timing, not results): NOLOAD never
-// refreshes the operands after the prologue, HALFB refreshes only A (the
-// load path's share of the kernel time)
-#ifdef OCM_G8_DIAG_NOLOAD  // diagnostic build only (make exp): operands never refreshed after the prologue
-#define Q8D_REFILL(NA, NB, STG) (void)0
-#elif defined(OCM_G8_DIAG_HALFB)  // diagnostic: B operands never refreshed (half the loads)
-#define Q8D_REFILL(NA, NB, STG)                                                                       \
-  do {                                                                                              \
-    const int so_ = (STG) * (int)gstride;                                                           \
-    _Pragma("unroll") for (int x_ = 0; x_ < 2; ++x_)                                                \
-    _Pragma("unroll") for (int dg_ = 0; dg_ < 3; ++dg_)                                             \
-      NA[x_][dg_] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ra[dg_], voff + x_ * 1024, so_, 0); \
-  } while (0)
-#else
-#define Q8D_REFILL(NA, NB, STG) Q8D_LOAD(NA, NB, STG)
-#endif
-#if !defined(OCM_G8_BURST) && !defined(OCM_G8_DIAG_NOLOAD) && !defined(OCM_G8_DIAG_HALFB)
   // the 12 refill loads of stage STG+2 interleaved one per two MFMAs of stage
   // STG, in the order the next stages consume them: 399 vs 387 TF for the
-  // loads issued as one burst before the MFMAs (OCM_G8_BURST, exp builds)
+  // loads issued as one burst before the MFMAs.  z: first stage of a scale
+  // block — each accumulator's first product starts from an inline zero (no
+  // separate reset after the flush)
   auto step_il = [&](i32x4 (&CA)[2][3], i32x4 (&CB)[2][3], i32x4 (&NA)[2][3], i32x4 (&NB)[2][3], int stg,
                      bool z) __attribute__((always_inline)) {
     const int so_ = min(stg + 2, nstage3 - 1) * (int)gstride;
@@ -1794,50 +1684,28 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-#define Q8D_STEP_(STG, Z, CA, CB, NA, NB) step_il(CA, CB, NA, NB, (STG), (Z))
-#else
-#define Q8D_STEP_(STG, Z, CA, CB, NA, NB)                                                             \
-  do {                                                                                              \
-    Q8D_REFILL(NA, NB, min((STG) + 2, nstage3 - 1));                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    Q8D_MFMA(CA, CB, Z);                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-  } while (0)
-#endif
-#define Q8D_STEP(STG, Z, ...) Q8D_STEP_(STG, Z, __VA_ARGS__)
 
   i32x4 F0A[2][3], F0B[2][3], F1A[2][3], F1B[2][3], F2A[2][3], F2B[2][3];
   Q8D_LOAD(F0A, F0B, 0);
   Q8D_LOAD(F1A, F1B, min(1, nstage3 - 1));
-#if defined(OCM_G8_DIAG_NOLOAD) || defined(OCM_G8_DIAG_HALFB)
-  Q8D_LOAD(F2A, F2B, min(2, nstage3 - 1));
-#endif
   for (int blk = 0; blk < nb; ++blk) {
-    // stage s0+u uses set u % 3 (s0 is a multiple of 48); the loads of stage
-    // s0+u+2 go to set (u+2) % 3.  The block's scales are fetched early (they
+    // stage s0+u computes on set u % 3 (s0 is a multiple of 48); the loads of
+    // stage s0+u+2 go to set (u+2) % 3.  The block's scales are fetched early (they
     // are used by the flush after the last stage).
     const int s0 = blk * Q8SPB;
 #pragma unroll
     for (int u = 0; u < Q8SPB; u += 3) {
-      Q8D_STEP(s0 + u, u == 0, Q8D_S0);
-      Q8D_STEP(s0 + u + 1, false, Q8D_S1);
+      step_il(F0A, F0B, F2A, F2B, s0 + u, u == 0);
+      step_il(F1A, F1B, F0A, F0B, s0 + u + 1, false);
       if (u == 0) {
         SR = srow[(size_t)blk * q.P8];
         SC = scol[(size_t)blk * q.P8];
       }
-      Q8D_STEP(s0 + u + 2, false, Q8D_S2);
+      step_il(F2A, F2B, F1A, F1B, s0 + u + 2, false);
     }
     flush();
   }
-#undef Q8D_STEP
-#undef Q8D_STEP_
-#undef Q8D_REFILL
-#undef Q8D_S0
-#undef Q8D_S1
-#undef Q8D_S2
-#undef Q8D_MFMA
 #undef Q8D_LOAD
-#undef Q8D_LOAD_B
 
   float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
 #pragma unroll
@@ -1852,37 +1720,9 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
       }
 }
 
-// ---------------------------------------------------------------------------
-// k_gram8e (persistent, below) and k_gram8w (one item per workgroup: the
-// launch before it, `make exp` builds only, its A/B partner) — k_gram8d's
-// work on the 16×16×64 integer MFMA (v_mfma_i32_16x16x64_i8, 16 cycles) instead of 32×32×32 (32 cycles): 419
-// vs 386 TF in one process (r03q; the chip holds a higher clock on the
-// 16×16 shape).  Same digit planes, 64×64 wave blocks, band order, three
-// int32 sets and f32 running sums, so the partials are bit for bit those of
-// k_gram8d (the int32 sums are exact; each element's f32 flushes run in the
-// same order).  Default order: a workgroup item is one tile's four blocks
-// (off-diagonal tiles first, then the diagonal ones packed) and its waves
-// meet at a barrier every two stages — a fragment is then loaded by two
-// waves of one CU at about the same time and the L1 serves one of them
-// (the L2 → CU path is the limit: at full MFMA rate a CU would take 64 B/clk
-// of fragments from it).  A stage is 64 rows (two 32-row digit
-// groups): lane (c, g) of a fragment holds column c (0..15) of a 16-column
-// sub-panel, bytes 16(g & 1) .. +15 of group g >> 1 — the voffset picks the
-// group, so the quantiser's layout is unchanged.  Per stage a wave loads 24
-// fragments (4 sub-panels × 3 digits for A and for B) for 96 MFMAs, one load
-// per four MFMAs, one stage ahead into the other of two register sets.
-// ---------------------------------------------------------------------------
-// SKIP (the θ3 trace Gram's instantiation only): a chunk stops at its last
-// row's stage pair instead of running its last block's zero-padded stages —
-// the trace Gram takes all its rows as ONE chunk (a 2048-row Gram of 136 tiles
-// as two chunks was 272 workgroups: 34 per XCD of 32 CUs, two rounds of 24
-// stages) and so runs 24 + 8 stages in one round.  Not in the headline
-// instantiation: the branch in the unrolled stage loop cost it 3 %
-// (profiles/r05s9_gram_stage_skip_ab.txt).
 #ifdef OCM_G8E_STAMPS  // diagnostic build (make exp): Σ over workgroup items of wave 0's wall-clock stamps (100 MHz)
 // [0] entry → first MFMA can issue (its operands have arrived), [1] last MFMA
-// → the item's end (last flush; the one-item kernel: its stores issued),
-// [2] entry → end, [3] items
+// → the item's end (last flush), [2] entry → end, [3] items
 __device__ unsigned long long g8_stamp_acc[4];
 #define G8_STAMP(V) const uint64_t V = __builtin_amdgcn_s_memrealtime()
 #define G8_STAMP_VAR(V) uint64_t V = 0
@@ -1901,211 +1741,72 @@ __device__ unsigned long long g8_stamp_acc[4];
 #define G8_STAMP_SUM(A, B, C, D)
 #endif
 
-#ifdef OCM_EXP_SELECTORS  // the product launches k_gram8e (below)
-template <bool ALIGNED, int SYNC, bool FRONT = false, bool SKIP = false>
-__global__ __launch_bounds__(256, 1) void k_gram8w(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
-                                                   int nwg, int nblocks, float* __restrict__ part, int chunk0) {
-  __shared__ __attribute__((aligned(16))) float scl[4][2 * 64];      // wave-private: row, column scales
-  __shared__ __attribute__((aligned(16))) float runl[4][16][64][4];  // wave-private f32 running sums
-
-  G8_STAMP(t_in);
-  const int b = blockIdx.x;
-  // XCD-aware remap (each XCD a contiguous range of chunks); chunk0 < 0 (A/B
-  // only): dispatch order, the eight XCDs on neighbouring tiles of one chunk
-  const int wg = chunk0 < 0 ? b : ocm_g8::logical_item(total_wg, b);
-  const int cl = wg / nwg, chunk = (chunk0 < 0 ? 0 : chunk0) + cl;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // SYNC > 0: a workgroup barrier every SYNC stages keeps the four waves in
-  // step, so the second wave's load of a shared panel fragment finds it in
-  // the CU's L1; a wave past the last block then computes a copy of the last
-  // block (never stored) instead of leaving.  ALIGNED (ocm_gram_map.h): a
-  // workgroup's four waves are one off-diagonal tile's four blocks, so each
-  // A and B panel fragment is fetched by two waves of the same CU.
-  int ti, tj, wm, wn;
-  bool dead;
-  if (ALIGNED) {
-    const ocm_g8::Block k = ocm_g8::block_tile(nt, ntiles, nblocks, wg - cl * nwg, wave);
-    ti = k.ti, tj = k.tj, wm = k.wm, wn = k.wn, dead = k.dead;
-    if (dead && SYNC == 0) return;
-  } else {
-    int bi = (wg - cl * nwg) * 4 + wave;
-    dead = bi >= nblocks;
-    if (dead && SYNC == 0) return;
-    if (dead) bi = nblocks - 1;
-    ocm_g8::packed_block(nt, bi, ti, tj, wm, wn);
-  }
-  const int tile = ti * nt - ti * (ti - 1) / 2 + (tj - ti);
-  const int I = ti * Q8T, J = tj * Q8T;
-  int s = 0;
-  while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
-  const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
-  const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
-  const int nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
-  constexpr int SPB = Q8BLK / 64;  // 64-row stages per scale block (24)
-  const int nstage = nb * SPB;
-  const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
-
-  const int lane = threadIdx.x & 63;
-  const int l15 = lane & 15, g4 = lane >> 4;
-  const size_t gstride = (size_t)q.P8 * 32;
-  const uint32_t span = (uint32_t)((size_t)nb * Q8SPB * gstride);
-  const char* cbase = q.digits + gbase * gstride;
-  __amdgpu_buffer_rsrc_t ra[3], rb[3];
-#pragma unroll
-  for (int dg = 0; dg < 3; ++dg) {
-    ra[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)(I + wm * 64) * 32), 0, span,
-                                               0x00020000);
-    rb[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)(J + wn * 64) * 32), 0, span,
-                                               0x00020000);
-  }
-  // sub-panel x of the wave's 64 columns: column 16x + l15, group g4 >> 1, half g4 & 1
-  const int voff = (g4 >> 1) * (int)gstride + l15 * 32 + (g4 & 1) * 16;
-  const int sstride = 2 * (int)gstride;
-  const float* srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I + wm * 64 + lane;
-  const float* scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J + wn * 64 + lane;
-
-  i32x4 acc1[4][4], acc2[4][4], acc3[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      acc1[a][c] = i32x4{};
-      acc2[a][c] = i32x4{};
-      acc3[a][c] = i32x4{};
-      *reinterpret_cast<f32x4*>(&runl[wave][a * 4 + c][lane][0]) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  float SR = 0.f, SC = 0.f;
-  auto flush = [&]() __attribute__((always_inline)) {
-    constexpr float w2 = 1.f / 254.f, w3 = 1.f / (254.f * 254.f);
-    scl[wave][lane] = SR;  // wave-private: LDS is in order within the wave
-    scl[wave][64 + lane] = SC;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      // row scales of registers 0..3: rows 16a + 4g4 + 0..3
-      const f32x4 si = *reinterpret_cast<const f32x4*>(&scl[wave][a * 16 + 4 * g4]);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float sj = scl[wave][64 + c * 16 + l15];
-        f32x4* rp = reinterpret_cast<f32x4*>(&runl[wave][a * 4 + c][lane][0]);
-        f32x4 rv = *rp;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = fmaf((float)acc3[a][c][e], w3, fmaf((float)acc2[a][c][e], w2, (float)acc1[a][c][e]));
-          rv[e] = fmaf(v, si[e] * sj, rv[e]);
-        }
-        *rp = rv;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // fragment load i (0..23) of a stage, in the order the stage's MFMAs first
-  // use them: A0, B0, B1, B2, B3, A1, A2, A3 (three digits each)
-  auto load_frag = [&](i32x4 (&FA)[4][3], i32x4 (&FB)[4][3], int i, int so) __attribute__((always_inline)) {
-    const int grp = i / 3, dg = i % 3;
-    if (grp >= 1 && grp <= 4)
-      FB[grp - 1][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rb[dg], voff + (grp - 1) * 512, so, 0);
-    else {
-      const int x = grp == 0 ? 0 : grp - 4;
-      FA[x][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ra[dg], voff + x * 512, so, 0);
-    }
-  };
-  // one stage: 96 MFMAs on (CA, CB), sub-blocks row-major, six products each;
-  // the 24 loads of the next stage into (NA, NB), one per four MFMAs
-  auto step = [&](i32x4 (&CA)[4][3], i32x4 (&CB)[4][3], i32x4 (&NA)[4][3], i32x4 (&NB)[4][3], int stg,
-                  bool z) __attribute__((always_inline)) {
-    const int so = min(stg + 1, nstage - 1) * sstride;
-    // FRONT (A/B only): the 24 loads one per two MFMAs over the first half of
-    // the stage instead of one per four over the whole stage — 392 vs 439 TF
-    constexpr int GRP = FRONT ? 48 : 24, PER = 96 / GRP;
-#pragma unroll
-    for (int i = 0; i < GRP; ++i) {
-#ifndef OCM_G8E_DIAG_NOLOAD  // diagnostic build only (make exp): operands never refreshed (timing, not results)
-      if (i < 24) load_frag(NA, NB, i, so);
-#else
-      (void)so;
-#endif
-#pragma unroll
-      for (int jj = 0; jj < PER; ++jj) {
-        const int j = PER * i + jj, blk = j / 6, kind = j % 6, a = blk >> 2, c = blk & 3;
-        if (kind == 0) acc1[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][0], z ? i32x4{} : acc1[a][c], 0, 0, 0);
-        if (kind == 1) acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][1], z ? i32x4{} : acc2[a][c], 0, 0, 0);
-        if (kind == 2) acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][1], CB[c][0], acc2[a][c], 0, 0, 0);
-        if (kind == 3) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][0], CB[c][2], z ? i32x4{} : acc3[a][c], 0, 0, 0);
-        if (kind == 4) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][2], CB[c][0], acc3[a][c], 0, 0, 0);
-        if (kind == 5) acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(CA[a][1], CB[c][1], acc3[a][c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (SYNC > 0 && stg % SYNC == SYNC - 1) __builtin_amdgcn_s_barrier();
-  };
-
-  const int nvs = SKIP ? (int)((r1 - r0 + 63) / 64) : nstage;  // stages holding rows (the rest are zero digits)
-  i32x4 F0A[4][3], F0B[4][3], F1A[4][3], F1B[4][3];
-#pragma unroll
-  for (int i = 0; i < 24; ++i) load_frag(F0A, F0B, i, 0);
-#ifdef OCM_G8E_STAMPS
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stage-0 operands are here
-#endif
-  G8_STAMP(t_first);
-  G8_STAMP_VAR(t_last);
-  for (int blk = 0; blk < nb; ++blk) {
-    const int s0 = blk * SPB;
-#pragma unroll
-    for (int u = 0; u < SPB; u += 2) {
-      if (SKIP && u > 0 && s0 + u >= nvs) break;
-      step(F0A, F0B, F1A, F1B, s0 + u, u == 0);
-      if (u == 0) {
-        SR = srow[(size_t)blk * q.P8];
-        SC = scol[(size_t)blk * q.P8];
-      }
-      step(F1A, F1B, F0A, F0B, s0 + u + 1, false);
-    }
-    G8_STAMP_SET(t_last);
-    flush();
-  }
-
-  if (!dead) {
-    float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = wm * 64 + a * 16 + 4 * g4 + e;
-          const int col = wn * 64 + c * 16 + l15;
-          out[row * Q8T + col] = runl[wave][a * 4 + c][lane][e];
-        }
-  }
-  G8_STAMP(t_out);
-  G8_STAMP_SUM(t_in, t_first, t_last, t_out);
-}
-#endif  // OCM_EXP_SELECTORS
-
 // ---------------------------------------------------------------------------
-// k_gram8e — k_gram8w<ALIGNED, SYNC = 2> as a persistent kernel: one workgroup
-// per CU walks its share of the (chunk, tile) items (ocm_gram_map.h, `map`:
-// MAP_RANGE, static striding inside each XCD's contiguous range, in the order
-// the one-item launch dispatched them, or MAP_ROUND, rounds of gridDim.x
-// consecutive items that all XCDs sweep together; either way from blockIdx
-// alone: no counter, nothing to reset, capture-safe).  What
-// a workgroup used to pay around its stage loop now runs beside MFMAs:
+// k_gram8e — the product's i8×3 Gram: k_gram8d's work on the 16×16×64 integer
+// MFMA, tile-aligned workgroup items, waves kept in step, persistent launch.
+//
+// Shape.  v_mfma_i32_16x16x64_i8 (16 cycles) instead of 32×32×32 (32 cycles):
+// 419 vs 386 TF in one process (r03q; the chip holds a higher clock on the
+// 16×16 shape).  Same digit planes, 64×64 wave blocks, band order, three
+// int32 sets and f32 running sums as k_gram8d, so the partials are bit for
+// bit k_gram8d's (the int32 sums are exact; each element's f32 flushes run in
+// the same order).  A stage is 64 rows (two 32-row digit groups): lane (c, g)
+// of a fragment holds column c (0..15) of a 16-column sub-panel, bytes
+// 16(g & 1) .. +15 of group g >> 1 — the voffset picks the group, so the
+// quantiser's layout is unchanged.
+//
+// Item order (tile-aligned, ocm_gram_map.h block_of).  A workgroup item is
+// four consecutive 64×64 blocks of a chunk's block list: the off-diagonal
+// tiles first, in band order, four blocks each — so the four waves are one
+// tile's four blocks and every A and B panel fragment is wanted by two waves
+// of the same CU — then the diagonal tiles, three blocks each, packed.  A
+// wave past the chunk's last block computes a copy of the last block and
+// stores nothing (it must stay for the barriers).
+//
+// Barrier every two stages.  The L1 is 32 KB per CU and a wave streams 24 KiB
+// of fragments per stage, so the second wave's load of a shared fragment
+// finds it in the L1 only if the two load it at about the same time (the
+// L2 → CU path is the limit: at full MFMA rate a CU would take 64 B/clk of
+// fragments from it).  Aligned items alone gained nothing (413–415 vs 417
+// TF); with a barrier every stage 434–437, every two stages 437–445 TF;
+// every 3 or 4 stages within the spread.
+//
+// Register pipeline.  Per stage a wave loads 24 fragments (4 sub-panels × 3
+// digits for A and for B) for 96 MFMAs, one load per four MFMAs over the
+// whole stage, one stage ahead into the other of two register sets (F0, F1).
+// The loads one per two MFMAs over the stage's first half: 392 vs 439 TF
+// (DESIGN §8).  Workgroup ids are remapped so that an XCD works on
+// neighbouring items and shares its L2 (dispatch order: 417 vs 444 TF).
+//
+// Persistent launch.  One workgroup per CU walks its share of the (chunk,
+// tile) items (ocm_gram_map.h, `map`: MAP_RANGE, static striding inside each
+// XCD's contiguous range, or MAP_ROUND, rounds of gridDim.x consecutive items
+// that all XCDs sweep together; either way from blockIdx alone: no counter,
+// nothing to reset, capture-safe).  What one workgroup per item paid around
+// its stage loop (≈ 10 µs in 85) runs beside MFMAs: 448–455
+// against 435–442 TF.
 //   * the band walk is done once per workgroup into an LDS table;
-//   * the 24 load slots of an item's last stage (clamped duplicates in
-//     k_gram8w) fetch stage 0 of the workgroup's next item, through that
-//     item's descriptors (scalar selects at that one unrolled position, no
-//     branch in the stage loop);
+//   * the 24 load slots of an item's last stage (there is no next stage of
+//     its own to load) fetch stage 0 of the workgroup's next item, through
+//     that item's descriptors (scalar selects at that one unrolled position,
+//     no branch in the stage loop);
 //   * the running sums need no zero pass: an item's first flush adds to +0
 //     (fmaf(v, s, +0.f), the same bits as adding to a zeroed sum);
 //   * an item's runl → part stores ride between the MFMAs of the next item's
 //     stage 0 (a second copy of that one stage, chosen by one uniform branch
 //     per scale block), through a buffer descriptor that is empty for a dead
 //     wave: out-of-range buffer stores are dropped.
-// Same integer sums, same f32 flush order per element: bit for bit the
-// partials of k_gram8d/8e.  The four waves take the same items, and their
-// stage and barrier counts come from the chunk alone (workgroup-uniform).
-// SKIP (θ3 trace Gram, 136 items: one per workgroup on this chip): no
-// cross-item prefetch, an item's stage 0 is loaded at its start.
+// The four waves take the same items, and their stage and barrier counts come
+// from the chunk alone (workgroup-uniform).
+//
+// SKIP (the θ3 trace Gram's instantiation only; 136 items: one per workgroup
+// on this chip): a chunk stops at its last row's stage pair instead of
+// running its last block's zero-padded stages — the trace Gram takes all its
+// rows as ONE chunk (a 2048-row Gram of 136 tiles as two chunks was 272
+// workgroups: 34 per XCD of 32 CUs, two rounds of 24 stages) and so runs
+// 24 + 8 stages in one round.  No cross-item prefetch: an item's stage 0 is
+// loaded at its start.  Not in the headline instantiation: the branch in the
+// unrolled stage loop cost it 3 % (profiles/r05s9_gram_stage_skip_ab.txt).
 // ---------------------------------------------------------------------------
 // cache-policy bits of the partials' stores (A/B builds: 2 = non-temporal)
 #ifndef OCM_G8E_STORE_AUX
@@ -2334,425 +2035,6 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
   for (int i = 0; i < 16; ++i) store_sub(*reinterpret_cast<const f32x4*>(&runl[wave][i][lane][0]), i, rpend);
 }
 
-#ifdef OCM_G8_LDS
-// ---------------------------------------------------------------------------
-// k_gram8x (experiment, make exp only: OCM_GRAM8_ORDER=lds) — k_gram8w with
-// the panels shared through LDS.  Measured (r03u, r03v): bit-identical, 362–367
-// TF against the default launch's 439–445 in the same processes, with the
-// partner reads as one burst or split — not kept.  One workgroup per
-// 128×128 tile (off-diagonal tiles in band order, then the diagonal ones; a
-// diagonal tile's mirror wave loads and stages its share but computes
-// nothing).  Waves (wm, wn) and (wm, 1−wn) need the same A panel, (wm, wn)
-// and (1−wm, wn) the same B panel: each wave loads only half of its 24
-// fragments per 64-row stage from global memory (A sub-panels 2wn, 2wn+1 and
-// B sub-panels 2wm, 2wm+1: its "own" 12), writes them to a two-slot LDS ring
-// and reads the other 12 from its partners' slots, so the L2 → CU traffic is
-// halved.  Stage t: read the partners' fragments of t (written before the
-// barrier that ended stage t−1); the 24 MFMAs of own × own sub-blocks cover
-// that read; the own loads of stage t+2 go out one per MFMA group, and the
-// own fragments of t+1 (loaded during t−1) are written to the other slot
-// during the last 72 MFMAs; lgkmcnt(0) + barrier.  Sub-block indices are kept
-// relative (own first): actual sub-panel = relative ^ (2·wn) for A and
-// ^ (2·wm) for B, applied to the load offsets and the output positions only.
-// Same exact int32 sets and f32 flush order as k_gram8d/8e: bit-identical.
-// ---------------------------------------------------------------------------
-constexpr int G8X_FRAG = 1024, G8X_WSLOT = 12 * G8X_FRAG, G8X_SLOT = 4 * G8X_WSLOT;
-__global__ __launch_bounds__(256, 1) void k_gram8x(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
-                                                   float* __restrict__ part) {
-  __shared__ __attribute__((aligned(1024))) char ring[2 * G8X_SLOT];     // 96 KiB
-  __shared__ __attribute__((aligned(16))) float runl[4][16][64][4];      // 64 KiB: wave-private f32 running sums
-
-  const int b = blockIdx.x;
-  const int q8 = total_wg / 8, r8 = total_wg % 8, x8 = b % 8;
-  const int wg = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
-  const int chunk = wg / ntiles;
-  const int tix = wg - chunk * ntiles;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  int ti = -1, tj = 0;
-  if (tix < ntiles - nt) {
-    int rem = tix;
-    for (int u = 0; u < nt && ti < 0; u += G8_BAND_R)
-      for (int v = u; v < nt && ti < 0; v += G8_BAND_C)
-        for (int a = u; a < min(nt, u + G8_BAND_R) && ti < 0; ++a)
-          for (int c = max(v, a + 1); c < min(nt, v + G8_BAND_C); ++c) {
-            if (rem == 0) {
-              ti = a;
-              tj = c;
-              break;
-            }
-            --rem;
-          }
-  } else {
-    ti = tj = tix - (ntiles - nt);
-  }
-  const bool mirror = (ti == tj) && wm == 1 && wn == 0;  // a diagonal tile's strictly-lower block
-  const int tile = ti * nt - ti * (ti - 1) / 2 + (tj - ti);
-  const int I = ti * Q8T, J = tj * Q8T;
-  int s = 0;
-  while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
-  const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
-  const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
-  const int nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
-  constexpr int SPB = Q8BLK / 64;  // 64-row stages per scale block (24, a multiple of 3)
-  const int nstage = nb * SPB;
-  const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
-
-  const int lane = threadIdx.x & 63;
-  const int l15 = lane & 15, g4 = lane >> 4;
-  const size_t gstride = (size_t)q.P8 * 32;
-  const uint32_t span = (uint32_t)((size_t)nb * Q8SPB * gstride);
-  const char* cbase = q.digits + gbase * gstride;
-  __amdgpu_buffer_rsrc_t ra[3], rb[3];
-#pragma unroll
-  for (int dg = 0; dg < 3; ++dg) {
-    ra[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)(I + wm * 64) * 32), 0, span,
-                                               0x00020000);
-    rb[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)(J + wn * 64) * 32), 0, span,
-                                               0x00020000);
-  }
-  // own sub-panels: A 2wn + j, B 2wm + j (j = 0, 1)
-  const int voff = (g4 >> 1) * (int)gstride + l15 * 32 + (g4 & 1) * 16;
-  const int voffA = voff + 2 * wn * 512, voffB = voff + 2 * wm * 512;
-  const int sstride = 2 * (int)gstride;
-  const float* srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I + wm * 64 + lane;
-  const float* scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J + wn * 64 + lane;
-  // LDS: own fragment i of slot u at ring + u·SLOT + wave·WSLOT + i·FRAG;
-  // partner A fragments from wave ^ 1 (its own A, indices 0..5), partner B
-  // from wave ^ 2 (its own B, indices 6..11)
-  char* const wr_base = ring + wave * G8X_WSLOT + lane * 16;
-  const char* const rdA_base = ring + (wave ^ 1) * G8X_WSLOT + lane * 16;
-  const char* const rdB_base = ring + (wave ^ 2) * G8X_WSLOT + 6 * G8X_FRAG + lane * 16;
-
-  i32x4 acc1[4][4], acc2[4][4], acc3[4][4];  // [relative a][relative c]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      acc1[a][c] = i32x4{};
-      acc2[a][c] = i32x4{};
-      acc3[a][c] = i32x4{};
-      *reinterpret_cast<f32x4*>(&runl[wave][a * 4 + c][lane][0]) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  float SR = 0.f, SC = 0.f;
-  auto flush = [&]() __attribute__((always_inline)) {
-    constexpr float w2 = 1.f / 254.f, w3 = 1.f / (254.f * 254.f);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int aa = a ^ (2 * wn);  // actual sub-panel: rows 16aa + 4g4 + e
-      f32x4 si;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) si[e] = __shfl(SR, aa * 16 + 4 * g4 + e);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float sj = __shfl(SC, (c ^ (2 * wm)) * 16 + l15);
-        f32x4* rp = reinterpret_cast<f32x4*>(&runl[wave][a * 4 + c][lane][0]);
-        f32x4 rv = *rp;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = fmaf((float)acc3[a][c][e], w3, fmaf((float)acc2[a][c][e], w2, (float)acc1[a][c][e]));
-          rv[e] = fmaf(v, si[e] * sj, rv[e]);
-        }
-        *rp = rv;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // own fragment i (0..5: A j = i / 3, 6..11: B j = (i − 6) / 3; digit i % 3)
-  auto gload = [&](i32x4 (&OA)[2][3], i32x4 (&OB)[2][3], int i, int so) __attribute__((always_inline)) {
-    const int j = (i % 6) / 3, dg = i % 3;
-    if (i < 6)
-      OA[j][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ra[dg], voffA + j * 512, so, 0);
-    else
-      OB[j][dg] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rb[dg], voffB + j * 512, so, 0);
-  };
-  auto mfma6 = [&](const i32x4 (&A)[3], const i32x4 (&B)[3], int a, int c, bool z) __attribute__((always_inline)) {
-    acc1[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], B[0], z ? i32x4{} : acc1[a][c], 0, 0, 0);
-    acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], B[1], z ? i32x4{} : acc2[a][c], 0, 0, 0);
-    acc2[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1], B[0], acc2[a][c], 0, 0, 0);
-    acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], B[2], z ? i32x4{} : acc3[a][c], 0, 0, 0);
-    acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2], B[0], acc3[a][c], 0, 0, 0);
-    acc3[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1], B[1], acc3[a][c], 0, 0, 0);
-  };
-  i32x4 PA[2][3], PB[2][3];  // partner fragments of the current stage
-  // stage t: CUR = own(t), NXT = own(t+1) (landed, staged to LDS during t),
-  // FUT = own(t+2) (loaded during t)
-  auto step = [&](i32x4 (&CA)[2][3], i32x4 (&CB)[2][3], i32x4 (&NA)[2][3], i32x4 (&NB)[2][3], i32x4 (&FA)[2][3],
-                  i32x4 (&FB)[2][3], int stg, bool z) __attribute__((always_inline)) {
-    const int rs = (stg & 1) * G8X_SLOT, ws = ((stg + 1) & 1) * G8X_SLOT;
-    const int so = min(stg + 2, nstage - 1) * sstride;
-    // partner B (used from the second quarter) first, partner A (third
-    // quarter) two sub-blocks later: the LDS read burst is spread
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int dg = 0; dg < 3; ++dg)
-        PB[j][dg] = *reinterpret_cast<const i32x4*>(rdB_base + rs + (j * 3 + dg) * G8X_FRAG);
-    // 16 sub-blocks in four quarters: own × own, own × partner, partner × own, partner × partner
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int qd = g >> 2, a = g & 1 ? 1 : 0, c = (g >> 1) & 1;
-      if (g == 2) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int dg = 0; dg < 3; ++dg)
-            PA[j][dg] = *reinterpret_cast<const i32x4*>(rdA_base + rs + (j * 3 + dg) * G8X_FRAG);
-      }
-      if (g < 12) gload(FA, FB, g, so);
-      if (g >= 4) {
-        const int i = g - 4;  // 12 staging writes over the last 12 sub-blocks
-        const int jj = (i % 6) / 3, dg = i % 3;
-        *reinterpret_cast<i32x4*>(wr_base + ws + i * G8X_FRAG) = i < 6 ? NA[jj][dg] : NB[jj][dg];
-      }
-      if (!mirror) {
-        if (qd == 0) mfma6(CA[a], CB[c], a, c, z);
-        if (qd == 1) mfma6(CA[a], PB[c], a, 2 + c, z);
-        if (qd == 2) mfma6(PA[a], CB[c], 2 + a, c, z);
-        if (qd == 3) mfma6(PA[a], PB[c], 2 + a, 2 + c, z);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-
-  i32x4 O0A[2][3], O0B[2][3], O1A[2][3], O1B[2][3], O2A[2][3], O2B[2][3];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) gload(O0A, O0B, i, 0);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) gload(O1A, O1B, i, min(1, nstage - 1) * sstride);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const int jj = (i % 6) / 3, dg = i % 3;
-    *reinterpret_cast<i32x4*>(wr_base + i * G8X_FRAG) = i < 6 ? O0A[jj][dg] : O0B[jj][dg];
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  for (int blk = 0; blk < nb; ++blk) {
-    const int s0 = blk * SPB;
-#pragma unroll
-    for (int u = 0; u < SPB; u += 3) {
-      step(O0A, O0B, O1A, O1B, O2A, O2B, s0 + u, u == 0);
-      if (u == 0) {
-        SR = srow[(size_t)blk * q.P8];
-        SC = scol[(size_t)blk * q.P8];
-      }
-      step(O1A, O1B, O2A, O2B, O0A, O0B, s0 + u + 1, false);
-      step(O2A, O2B, O0A, O0B, O1A, O1B, s0 + u + 2, false);
-    }
-    if (!mirror) flush();
-  }
-  if (mirror) return;
-  float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = wm * 64 + (a ^ (2 * wn)) * 16 + 4 * g4 + e;
-        const int col = wn * 64 + (c ^ (2 * wm)) * 16 + l15;
-        out[row * Q8T + col] = runl[wave][a * 4 + c][lane][e];
-      }
-}
-#endif  // OCM_G8_LDS
-
-#ifdef OCM_G8_LDS
-// ---------------------------------------------------------------------------
-// k_gram8s (experiment, make exp only) — the i8×3 Gram with the workgroup's
-// two 128-column panels shared through LDS.  One workgroup per 128×128 tile,
-// four waves of 64×64; each 64-row phase (two 32-row stages) of both panels
-// (48 KiB) is copied once into a 3-slot LDS ring by LDS-DMA
-// (global_load_lds_dwordx4: one 1-KiB fragment per wave-instruction, 12 per
-// wave per phase + the block's row/column scales into a 4-slot scale ring),
-// three phases ahead.  Each wave reads its fragments with ds_read_b128 one
-// stage ahead of the MFMAs that use them, one read per two MFMAs; one counted
-// vmcnt wait + one raw barrier per phase, between the two stages.  The fragment
-// image is lane-linear with the halves of column r swapped when bit 3 of r is
-// set (applied on the DMA source and on the read): conflict-free reads.
-// Measured (r02_lds, 1M × 2048): parity equal to k_gram8d (3.6e-8 vs fp64),
-// 305 TF against k_gram8d's 393 in the same process pair — halving the
-// vector-memory bytes per MFMA does not pay for the per-phase barrier; kept
-// for the next round's LDS / tile-order work, never in libocm.
-// ---------------------------------------------------------------------------
-constexpr int G8S_FRAG = 1024;
-constexpr int G8S_OPS = 2 * 2 * 3 * 4 * G8S_FRAG;  // [stage][A|B][digit][32-col block] = 48 KiB
-constexpr int G8S_NSLOT = 3;
-constexpr int G8S_SCL = 4 * 512;                   // [wave][64 row scales | 64 column scales]
-constexpr int G8S_NSCL = 4;
-
-// LDS-DMA with a scalar 64-bit base and a 32-bit per-lane offset (saddr form):
-// no per-lane 64-bit addresses to keep live across the loop
-__device__ __forceinline__ void g8s_dma16(const void* sbase, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds)
-               : "memory");
-}
-__device__ __forceinline__ void g8s_dma4(const void* sbase, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds)
-               : "memory");
-}
-
-__global__ __launch_bounds__(256, 1) void k_gram8s(Q8Plan q, SegTable st, int nt, int ntiles, int total_wg,
-                                                   float* __restrict__ part) {
-  __shared__ __attribute__((aligned(1024))) char lds[G8S_NSLOT * G8S_OPS + G8S_NSCL * G8S_SCL];
-
-  const int b = blockIdx.x;
-  const int q8 = total_wg / 8, r8 = total_wg % 8, x8 = b % 8;
-  const int wg = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
-  const int chunk = wg / ntiles;
-  const int tile = wg - chunk * ntiles;
-  int ti, tj;
-  tile_coords(tile, nt, ti, tj);
-  const int I = ti * Q8T, J = tj * Q8T;
-  int s = 0;
-  while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
-  const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
-  const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
-  const int nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
-  constexpr int PPB = Q8SPB / 2;  // phases per scale block
-  const int nph = nb * PPB;
-  const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, h = lane >> 5;
-  const bool skip = (ti == tj && wm > wn);  // the mirror block of a diagonal tile: computed, not stored
-  const size_t gstride = (size_t)q.P8 * 32;
-
-  // DMA role: stage (wave >> 1) of a phase, operand (wave & 1): 3 digits × 4 column blocks
-  const int sg_dma = wave >> 1, op_dma = wave & 1;
-  const uint32_t srcoff = (uint32_t)(lane >> 1) * 32 + 16 * ((lane & 1) ^ ((lane >> 4) & 1));
-  const char* dma_base = q.digits + (gbase + sg_dma) * gstride + (size_t)(op_dma ? J : I) * 32;
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-  const float* scl_src = q.scale + (size_t)chunk * q.nblk * q.P8;
-  const uint32_t scloff = (uint32_t)lane * 4;
-  const int srow0 = I + wm * 64, scol0 = J + wn * 64;
-
-  auto issue = [&](int ph) __attribute__((always_inline)) {
-    const int phc = min(ph, nph - 1);
-    const uint32_t sb = lds0 + (uint32_t)((ph % G8S_NSLOT) * G8S_OPS);
-    const size_t poff = (size_t)phc * 2 * gstride;
-#pragma unroll
-    for (int dg = 0; dg < 3; ++dg)
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-        g8s_dma16(dma_base + dg * q.plane + poff + x * G8S_FRAG, srcoff,
-                  sb + (((sg_dma * 2 + op_dma) * 3 + dg) * 4 + x) * G8S_FRAG);
-    const size_t so = (size_t)(phc / PPB) * q.P8;
-    const uint32_t scb = lds0 + (uint32_t)(G8S_NSLOT * G8S_OPS + (ph % G8S_NSCL) * G8S_SCL + wave * 512);
-    g8s_dma4(scl_src + so + srow0, scloff, scb);
-    g8s_dma4(scl_src + so + scol0, scloff, scb + 256);
-  };
-  const int rdoff = 16 * (2 * l31 + (h ^ ((l31 >> 3) & 1)));
-  auto frag = [&](int slot, int sg, int op, int dg, int xb) __attribute__((always_inline)) -> i32x4 {
-    return *reinterpret_cast<const i32x4*>(lds + slot * G8S_OPS + (((sg * 2 + op) * 3 + dg) * 4 + xb) * G8S_FRAG +
-                                           rdoff);
-  };
-
-  i32x16 acc1[2][2], acc2[2][2], acc3[2][2];
-  float run[2][2][16];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      acc1[a][c] = i32x16{};
-      acc2[a][c] = i32x16{};
-      acc3[a][c] = i32x16{};
-#pragma unroll
-      for (int r = 0; r < 16; ++r) run[a][c][r] = 0.f;
-    }
-  // one stage: 24 MFMAs on (CA, CB); the 12 fragments of the next stage read
-  // from LDS into (NA, NB), one per two MFMAs
-  auto half = [&](i32x4 (&CA)[2][3], i32x4 (&CB)[2][3], i32x4 (&NA)[2][3], i32x4 (&NB)[2][3], int rslot,
-                  int rsg) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      const int x = i / 6, r = i % 6, dg = r / 2;
-      if (r & 1)
-        NB[x][dg] = frag(rslot, rsg, 1, dg, 2 * wn + x);
-      else
-        NA[x][dg] = frag(rslot, rsg, 0, dg, 2 * wm + x);
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int j = 2 * i + jj, blk = j / 6, kind = j % 6, a = blk >> 1, c = blk & 1;
-        if (kind == 0) acc1[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][0], CB[c][0], acc1[a][c], 0, 0, 0);
-        if (kind == 1) acc2[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][0], CB[c][1], acc2[a][c], 0, 0, 0);
-        if (kind == 2) acc2[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][1], CB[c][0], acc2[a][c], 0, 0, 0);
-        if (kind == 3) acc3[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][0], CB[c][2], acc3[a][c], 0, 0, 0);
-        if (kind == 4) acc3[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][2], CB[c][0], acc3[a][c], 0, 0, 0);
-        if (kind == 5) acc3[a][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(CA[a][1], CB[c][1], acc3[a][c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-
-  i32x4 R0A[2][3], R0B[2][3], R1A[2][3], R1B[2][3];
-  issue(0);
-  issue(1);
-  issue(2);
-  asm volatile("s_waitcnt vmcnt(28)\n\ts_barrier" ::: "memory");  // phase 0 landed for every wave
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int dg = 0; dg < 3; ++dg) {
-      R0A[x][dg] = frag(0, 0, 0, dg, 2 * wm + x);
-      R0B[x][dg] = frag(0, 0, 1, dg, 2 * wn + x);
-    }
-  for (int ph = 0; ph < nph; ++ph) {
-    half(R0A, R0B, R1A, R1B, ph % G8S_NSLOT, 1);
-    // this wave's DMAs of phase ph+1 are done (those of ph+2 may fly); every
-    // wave's reads of slot ph%3 are done: it takes phase ph+3
-    asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    issue(ph + 3);
-    half(R1A, R1B, R0A, R0B, (ph + 1) % G8S_NSLOT, 0);
-    if (ph % PPB == PPB - 1) {
-      constexpr float w2 = 1.f / 254.f, w3 = 1.f / (254.f * 254.f);
-      const float* scl = reinterpret_cast<const float*>(lds + G8S_NSLOT * G8S_OPS + (ph % G8S_NSCL) * G8S_SCL +
-                                                        wave * 512);
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float sj = scl[64 + c * 32 + l31];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const f32x4 si = *reinterpret_cast<const f32x4*>(&scl[a * 32 + 8 * g + 4 * h]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int r = 4 * g + e;
-              const float v = fmaf((float)acc3[a][c][r], w3, fmaf((float)acc2[a][c][r], w2, (float)acc1[a][c][r]));
-              run[a][c][r] = fmaf(v, si[e] * sj, run[a][c][r]);
-            }
-          }
-          acc1[a][c] = i32x16{};
-          acc2[a][c] = i32x16{};
-          acc3[a][c] = i32x16{};
-        }
-      }
-    }
-  }
-  // no LDS-DMA may still be landing when the workgroup's LDS is released
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (skip) return;
-  float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int col = wn * 64 + c * 32 + l31;
-        out[row * Q8T + col] = run[a][c][r];
-      }
-}
-#endif  // OCM_G8_LDS
 
 int gram_small(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int32_t p, const float* shift,
                const int64_t* seg_offsets, int32_t nseg, double* G_out, double* colsum_out, hipStream_t st) {
@@ -2956,8 +2238,6 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     OCM_CHECK_LAUNCH("k_q8_thresholds");
   }
 
-  // all quantiser launches first, then the mark count is read back while the
-  // Gram runs
   std::vector<SegTable> tabs;
   std::vector<int> tab_s0;
   for (int s0 = 0; s0 < nseg; s0 += MAXSEG) {
@@ -2991,78 +2271,28 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   OCM_HIP(hipStreamIsCapturing(st, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  // The Gram's block order and wave sync: tile-aligned workgroups with a
-  // barrier every two stages (437 TF against 417 for the packed walk without
-  // barriers, r03s), as a persistent kernel (k_gram8e, one workgroup per CU).
-  // The product library launches only that variant; the A/B selectors
-  // (OCM_GRAM8_ORDER = wg | packed | aligned | sync1 | front | sync4 | sync3,
-  // OCM_GRAM8_XCD, OCM_GRAM8_MAP, OCM_GRAM8_PIECES, OCM_Q8_CG) exist only in `make exp`
-  // builds (OCM_EXP_SELECTORS), which the product never loads.  wg: the same
-  // order with one item per workgroup (k_gram8w), the launch before k_gram8e.
-  int order = 3;
-  bool no_remap = false;  // (k_gram8w launches only)
-  (void)no_remap;
-  int pieces = 1;
-  int qcg = 1;  // column groups per quantiser workgroup
-  // k_gram8e's work map (ocm_gram_map.h); OCM_GRAM8_MAP = range | round in exp builds
+  // k_gram8e's work map (ocm_gram_map.h); OCM_GRAM8_MAP = range | round in
+  // `make exp` builds (OCM_EXP_SELECTORS), which the product never loads
   int gmap = ocm_g8::MAP_ROUND;
 #ifdef OCM_EXP_SELECTORS
   if (const char* mv = getenv("OCM_GRAM8_MAP")) gmap = !strcmp(mv, "round") ? ocm_g8::MAP_ROUND : ocm_g8::MAP_RANGE;
-  const char* ord = getenv("OCM_GRAM8_ORDER");
-  if (ord && !strcmp(ord, "wg")) order = 9;
-  if (ord && !strcmp(ord, "packed")) order = 0;
-  if (ord && !strcmp(ord, "aligned")) order = 1;
-  if (ord && !strcmp(ord, "sync1")) order = 2;
-  if (ord && !strcmp(ord, "front")) order = 6;
-  if (ord && !strcmp(ord, "sync4")) order = 7;
-  if (ord && !strcmp(ord, "sync3")) order = 8;
-  const char* xr = getenv("OCM_GRAM8_XCD");  // "0": no XCD remap (A/B)
-  no_remap = xr && !strcmp(xr, "0");
-#ifdef OCM_G8_LDS
-  if (ord && !strcmp(ord, "lds")) order = 4;
-  if (ord && !strcmp(ord, "lds32")) order = 5;
 #endif
-  // Quantiser / Gram overlap (measured: no gain): the chunks are
-  // cut into `pieces` ranges; the quantiser of range i+1 runs on a side stream
-  // while the Gram of range i runs on the launch stream.
-  if (const char* pv = getenv("OCM_GRAM8_PIECES")) pieces = std::max(1, atoi(pv));
-  if (const char* qv = getenv("OCM_Q8_CG")) qcg = atoi(qv);
-#endif
-  if (capturing || k32 || unguarded || tabs.size() != 1) pieces = 1;
-  if (pieces > 1) {
-    const int64_t gch = cprefix[tab_s0[0] + tabs[0].nseg] - cprefix[tab_s0[0]];
-    pieces = (int)std::min<int64_t>(pieces, gch / 2);
-    if (pieces < 2) pieces = 1;
-  }
-  hipStream_t qs = st;  // the quantiser's stream
-  if (rows || (qcg != 2 && qcg != 4)) qcg = 1;
-  std::vector<hipEvent_t> qev;
-  if (pieces > 1) {
-    if (!ctx->side) OCM_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-    qs = ctx->side;
-    while ((int)ctx->fork_ev.size() < pieces + 1) {
-      hipEvent_t e;
-      OCM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ctx->fork_ev.push_back(e);
-    }
-    qev.assign(ctx->fork_ev.begin(), ctx->fork_ev.begin() + pieces + 1);
-    OCM_HIP(hipEventRecord(qev[pieces], st));  // everything queued before this call
-    OCM_HIP(hipStreamWaitEvent(qs, qev[pieces], 0));
-  }
   const int nblocks = 4 * ntiles - nt, nwg = (nblocks + 3) / 4;
-  auto quantise = [&](size_t t, int64_t c0, int64_t c1) {
+  auto tab_chunks = [&](size_t t) { return (int64_t)(cprefix[tab_s0[t] + tabs[t].nseg] - cprefix[tab_s0[t]]); };
+
+  // all quantiser launches first, then the mark count is read back while the
+  // Gram runs
+  for (size_t t = 0; t < tabs.size(); ++t) {
     const int s0 = tab_s0[t];
     const Q8Plan q = plan_for(s0);
     double* col_g = colpart + (size_t)cprefix[s0] * nblk * P8;
-    const int cgw = qcg;  // column groups per quantiser workgroup (P8 / 32 is a multiple of 4)
-    dim3 gq((unsigned)((c1 - c0) * nblk * cgw), (unsigned)(P8 / Q8QC / cgw));
-    ocm::TimedRegion tq(ctx, OCM_KERNEL_QUANT, qs, !unguarded);
+    const int ncg = P8 / Q8QC;
+    const unsigned nrb = (unsigned)(tab_chunks(t) * nblk);  // (chunk, scale block) pairs
+    ocm::TimedRegion tq(ctx, OCM_KERNEL_QUANT, st, !unguarded);
     if (prep) {
-      const int ncg = P8 / Q8QC;
-      const dim3 gp((unsigned)((c1 - c0) * nblk * ncg));
-#define Q8P_LAUNCH(G_, H_, W_)                                                                                \
-  hipLaunchKernelGGL((k_q8_quant_prep<G_, H_, W_>), gp, dim3(Q8QT), 0, qs, X, ldx, rows, p, shift, tabs[t], q, \
-                     col_g, (int)(c0 * nblk), ncg, pa, xout, ldo)
+#define Q8P_LAUNCH(G_, H_, W_)                                                                                     \
+  hipLaunchKernelGGL((k_q8_quant_prep<G_, H_, W_>), dim3(nrb * ncg), dim3(Q8QT), 0, st, X, ldx, rows, p, shift, tabs[t], \
+                     q, col_g, 0, ncg, pa, xout, ldo)
       if (pa.h == 0) {
         if (rows) Q8P_LAUNCH(true, 0, false); else if (xout) Q8P_LAUNCH(false, 0, true); else Q8P_LAUNCH(false, 0, false);
       } else if (pa.h == 2) {
@@ -3071,111 +2301,52 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
         if (rows) Q8P_LAUNCH(true, 7, false); else if (xout) Q8P_LAUNCH(false, 7, true); else Q8P_LAUNCH(false, 7, false);
       }
 #undef Q8P_LAUNCH
-    } else if (rows)
-      hipLaunchKernelGGL(k_q8_quant<true>, gq, dim3(Q8QT), 0, qs, X, ldx, rows, p, shift, tabs[t], q, col_g,
-                         (int)(c0 * nblk));
-#ifdef OCM_EXP_SELECTORS
-    else if (cgw == 4)
-      hipLaunchKernelGGL((k_q8_quant<false, 4>), gq, dim3(Q8QT), 0, qs, X, ldx, rows, p, shift, tabs[t], q, col_g,
-                         (int)(c0 * nblk));
-    else if (cgw == 2)
-      hipLaunchKernelGGL((k_q8_quant<false, 2>), gq, dim3(Q8QT), 0, qs, X, ldx, rows, p, shift, tabs[t], q, col_g,
-                         (int)(c0 * nblk));
-#endif
-    else
-      hipLaunchKernelGGL(k_q8_quant<false>, gq, dim3(Q8QT), 0, qs, X, ldx, rows, p, shift, tabs[t], q, col_g,
-                         (int)(c0 * nblk));
-  };
-  auto gram = [&](size_t t, int64_t c0, int64_t c1) {
+    } else if (rows) {
+      hipLaunchKernelGGL(k_q8_quant<true>, dim3(nrb, ncg), dim3(Q8QT), 0, st, X, ldx, rows, p, shift, tabs[t], q, col_g, 0);
+    } else {
+      hipLaunchKernelGGL(k_q8_quant<false>, dim3(nrb, ncg), dim3(Q8QT), 0, st, X, ldx, rows, p, shift, tabs[t], q, col_g, 0);
+    }
+  }
+  OCM_CHECK_LAUNCH("k_q8_quant");
+  hipEvent_t ev = nullptr;
+  const bool readback = !capturing && !unguarded;
+  if (readback) {
+    OCM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    OCM_HIP(hipMemcpyAsync(host, counters, 4, hipMemcpyDeviceToHost, st));
+    OCM_HIP(hipEventRecord(ev, st));
+  }
+  // The Gram: k_gram8e — tile-aligned items whose waves meet at a barrier
+  // every two stages (437 TF against 417 for the packed walk without barriers,
+  // r03s), persistent: one workgroup per CU (a CU holds one: ≈ 426 registers
+  // per lane), at least one per XCD so that every XCD's range of items is
+  // served.  k32 (OCM_GRAM_I8X3_K32): k_gram8d, one item per
+  // workgroup, the bit-for-bit reference on the 32×32×32 MFMA.
+  for (size_t t = 0; t < tabs.size(); ++t) {
     const int s0 = tab_s0[t];
-    const int64_t total = (c1 - c0) * nwg;
+    const int total = (int)(tab_chunks(t) * nwg);
     const Q8Plan q = plan_for(s0);
     float* pg = part + (size_t)cprefix[s0] * ntiles * Q8T * Q8T;
     ocm::TimedRegion tr(ctx, OCM_KERNEL_GRAM, st, !unguarded);
-#define G8E_LAUNCH(A_, S_)                                                                                   \
-  hipLaunchKernelGGL((k_gram8w<A_, S_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, \
-                     nwg, nblocks, pg, (no_remap && c0 == 0) ? -1 : (int)c0)
-#define G8E_LAUNCH3(A_, S_, F_)                                                                                      \
-  hipLaunchKernelGGL((k_gram8w<A_, S_, F_>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles,         \
-                     (int)total, nwg, nblocks, pg, (int)c0)
-    // one workgroup per CU (a CU holds one: ≈ 426 registers per lane); at
-    // least one per XCD, so that every XCD's range of items is served
-    const unsigned pgrid = (unsigned)std::min<int64_t>(total, std::max(ctx->num_cus, ocm_g8::NXCD));
-    if (tr_O && !k32 && order == 3)
-      hipLaunchKernelGGL(k_gram8e<true>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
-                         nblocks, pg, (int)c0, gmap);
-    else if (!k32 && order == 3)
-      hipLaunchKernelGGL(k_gram8e<false>, dim3(pgrid), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
-                         nblocks, pg, (int)c0, gmap);
-#ifdef OCM_EXP_SELECTORS
-    else if (tr_O && !k32 && order == 9)
-      hipLaunchKernelGGL((k_gram8w<true, 2, false, true>), dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt,
-                         ntiles, (int)total, nwg, nblocks, pg, (int)c0);
-    else if (!k32 && order == 9) G8E_LAUNCH(true, 2);
-    else if (!k32 && order == 0) G8E_LAUNCH(false, 0);
-    else if (!k32 && order == 1) G8E_LAUNCH(true, 0);
-    else if (!k32 && order == 2) G8E_LAUNCH(true, 1);
-    else if (!k32 && order == 6) G8E_LAUNCH3(true, 2, true);
-    else if (!k32 && order == 7) G8E_LAUNCH(true, 4);
-    else if (!k32 && order == 8) G8E_LAUNCH(true, 3);
-#endif
-#undef G8E_LAUNCH
-#undef G8E_LAUNCH3
-#ifdef OCM_G8_LDS
-    else if (!k32 && order >= 4 && order <= 5) {
-      const int64_t total_x = (c1 - c0) * ntiles;
-      if (order == 4)
-        hipLaunchKernelGGL(k_gram8x, dim3((unsigned)total_x), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total_x,
-                           pg);
-      else
-        hipLaunchKernelGGL(k_gram8s, dim3((unsigned)total_x), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total_x,
-                           pg);
-    }
-#endif
+    const dim3 pgrid((unsigned)std::min(total, std::max(ctx->num_cus, ocm_g8::NXCD)));
+    if (k32)
+      hipLaunchKernelGGL(k_gram8d, dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks,
+                         pg);
+    else if (tr_O)
+      hipLaunchKernelGGL(k_gram8e<true>, pgrid, dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks, pg, 0,
+                         gmap);
     else
-      hipLaunchKernelGGL(k_gram8d, dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, (int)total, nwg,
-                         nblocks, pg);
-  };
-  // all quantiser launches first (or, with pieces, range by range on the side
-  // stream), then the mark count is read back while the Gram runs
-  hipEvent_t ev = nullptr;
-  const bool readback = !capturing && !unguarded;
-  if (readback) OCM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  if (pieces == 1) {
-    for (size_t t = 0; t < tabs.size(); ++t) quantise(t, 0, cprefix[tab_s0[t] + tabs[t].nseg] - cprefix[tab_s0[t]]);
-    OCM_CHECK_LAUNCH("k_q8_quant");
-    if (readback) {
-      OCM_HIP(hipMemcpyAsync(host, counters, 4, hipMemcpyDeviceToHost, st));
-      OCM_HIP(hipEventRecord(ev, st));
-    }
-    for (size_t t = 0; t < tabs.size(); ++t) gram(t, 0, cprefix[tab_s0[t] + tabs[t].nseg] - cprefix[tab_s0[t]]);
-    OCM_CHECK_LAUNCH("k_gram8d/8p");
-  } else {
-    const int64_t gch = cprefix[tab_s0[0] + tabs[0].nseg] - cprefix[tab_s0[0]];
-    std::vector<int64_t> cut(pieces + 1);
-    for (int i = 0; i <= pieces; ++i) cut[i] = gch * i / pieces;
-    for (int i = 0; i < pieces; ++i) {
-      quantise(0, cut[i], cut[i + 1]);
-      OCM_HIP(hipEventRecord(qev[i], qs));
-    }
-    OCM_CHECK_LAUNCH("k_q8_quant");
-    OCM_HIP(hipMemcpyAsync(host, counters, 4, hipMemcpyDeviceToHost, qs));
-    OCM_HIP(hipEventRecord(ev, qs));
-    for (int i = 0; i < pieces; ++i) {
-      OCM_HIP(hipStreamWaitEvent(st, qev[i], 0));
-      gram(0, cut[i], cut[i + 1]);
-    }
-    OCM_CHECK_LAUNCH("k_gram8e");
-    OCM_HIP(hipStreamWaitEvent(st, ev, 0));  // the read-back is done before the workspace is reused
+      hipLaunchKernelGGL(k_gram8e<false>, pgrid, dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks, pg, 0,
+                         gmap);
   }
+  OCM_CHECK_LAUNCH("k_gram8d/8e");
 #ifdef OCM_G8E_STAMPS  // diagnostic build: the launch's stamp sums to stderr (10 ns units), then cleared
   {
     unsigned long long acc[4] = {0, 0, 0, 0};
     OCM_HIP(hipStreamSynchronize(st));
     OCM_HIP(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g8_stamp_acc), sizeof(acc)));
     if (!unguarded && !capturing && acc[3])
-      fprintf(stderr, "G8E_STAMPS order=%d items=%llu mean_us entry_to_first=%.3f last_to_end=%.3f entry_to_end=%.3f\n",
-              order, acc[3], 0.01 * acc[0] / acc[3], 0.01 * acc[1] / acc[3], 0.01 * acc[2] / acc[3]);
+      fprintf(stderr, "G8E_STAMPS items=%llu mean_us entry_to_first=%.3f last_to_end=%.3f entry_to_end=%.3f\n",
+              acc[3], 0.01 * acc[0] / acc[3], 0.01 * acc[1] / acc[3], 0.01 * acc[2] / acc[3]);
     const unsigned long long zero[4] = {0, 0, 0, 0};
     OCM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g8_stamp_acc), zero, sizeof(zero)));
   }

@@ -1,4 +1,4 @@
-// The work map of the i8×3 Gram kernels (k_gram8w, k_gram8e), shared by host
+// The work map of the i8×3 Gram kernels (k_gram8d, k_gram8e), shared by host
 // and device: which (chunk, tile, 64×64 block) a wave of a workgroup computes.
 // Plain C++ (no HIP types), so a host program can enumerate it
 // (tests/test_gram_workmap.py).
@@ -100,7 +100,7 @@ OCM_MAP_HD void offdiag_tile(int nt, int rank, int& ti, int& tj) {
         }
 }
 
-// packed walk (A/B launches only): every tile in band order, diagonal ones three blocks
+// packed walk (k_gram8d has the same loops inline): every tile in band order, diagonal ones three blocks
 OCM_MAP_HD void packed_block(int nt, int bi, int& ti, int& tj, int& wm, int& wn) {
   ti = -1;
   tj = wm = wn = 0;

@@ -26,9 +26,6 @@ struct ocm_ctx {
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[OCM_TIMED_KERNELS];
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-  // side stream + events of the quantiser / Gram overlap (created on first use)
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> fork_ev;
   // the eigensolver's θ work beside its Jacobi (created on first use): a side
   // stream, fork / join events, and a sub-context whose workspaces the θ3
   // Gram takes (the main workspace holds the eigensolver's live buffers)

@@ -4,15 +4,12 @@
 TFLOP/s (symmetric count n·p(p+1)) per mode/chunk and the max relative error
 of each mode against an fp64 Gram of a row sample.
 
-    python scripts/bench_gram.py [--variants i8x3:0,f32:0,bf16x3:0,i8x3:0:packed] [--outliers 0.005]
+    python scripts/bench_gram.py [--variants i8x3:0,f32:0,bf16x3:0,i8x3:0:range] [--outliers 0.005]
 
-A third field sets OCM_GRAM8_ORDER for that variant (k_gram8e block order),
-a fourth OCM_GRAM8_PIECES (quantiser / Gram overlap), a fifth OCM_Q8_CG
-(column groups per quantiser row block on consecutive workgroups), a sixth
-OCM_GRAM8_XCD (0: no XCD remap of the Gram workgroups), a seventh
-OCM_GRAM8_MAP (range | round: k_gram8e's work map).  The selectors are read by
-`make exp` libraries only (OCM_LIB=…, OCM_ALLOW_EXP_LIB=1).  "wall" is the whole
-call (guard, quantiser, Gram, reduce) between two device synchronisations.
+A third field sets OCM_GRAM8_MAP for that variant (range | round: k_gram8e's
+work map).  The selector is read by `make exp` libraries only (OCM_LIB=…,
+OCM_ALLOW_EXP_LIB=1).  "wall" is the whole call (guard, quantiser, Gram,
+reduce) between two device synchronisations.
 """
 import argparse
 import os
@@ -29,7 +26,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--p", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--variants", default="i8x3:0,bf16x3:0,f32:0", help="mode:chunk_rows[:order] (0 = automatic)")
+    ap.add_argument("--variants", default="i8x3:0,bf16x3:0,f32:0", help="mode:chunk_rows[:map] (0 = automatic)")
     ap.add_argument("--outliers", type=float, default=0.0, help="fraction of rows scaled x100..x1000")
     args = ap.parse_args()
     import torch
@@ -50,21 +47,19 @@ def main():
     ctx = Context.get(0)
     import time
 
-    variants = [tuple(v.split(":")[:2]) + tuple((v.split(":") + ["", "", "", "", ""])[2:7]) for v in args.variants.split(",")]
-    variants = [(m, int(c), o, pc, cg, xr, mp) for m, c, o, pc, cg, xr, mp in variants]
+    variants = [(v.split(":") + [""])[:3] for v in args.variants.split(",")]
+    variants = [(m, int(c), mp) for m, c, mp in variants]
     res = {":".join(map(str, v)): [] for v in variants}
     wall = {k: [] for k in res}
     quant = {k: [] for k in res}
     flop = args.rows * args.p * (args.p + 1)
     for _ in range(args.rounds):
-        for mode, chunk, order, pcs, qcg, xr, gmap in variants:
-            key = ":".join(map(str, (mode, chunk, order, pcs, qcg, xr, gmap)))
-            for var, val in (("OCM_GRAM8_ORDER", order), ("OCM_GRAM8_PIECES", pcs), ("OCM_Q8_CG", qcg),
-                             ("OCM_GRAM8_XCD", xr), ("OCM_GRAM8_MAP", gmap)):
-                if val:
-                    os.environ[var] = val
-                else:
-                    os.environ.pop(var, None)
+        for mode, chunk, gmap in variants:
+            key = ":".join(map(str, (mode, chunk, gmap)))
+            if gmap:
+                os.environ["OCM_GRAM8_MAP"] = gmap
+            else:
+                os.environ.pop("OCM_GRAM8_MAP", None)
             engine.gram(X, None, [0, args.rows], shift, mode=mode, chunk_rows=chunk)  # warm (workspace)
             torch.cuda.synchronize()
             ctx.read_timing(0)
@@ -84,10 +79,6 @@ def main():
     ns = min(args.rows, 65536)
     Y = X[:ns].double() - shift.double()
     Gref = Y.T @ Y
-    os.environ.pop("OCM_GRAM8_ORDER", None)
-    os.environ.pop("OCM_GRAM8_PIECES", None)
-    os.environ.pop("OCM_Q8_CG", None)
-    os.environ.pop("OCM_GRAM8_XCD", None)
     os.environ.pop("OCM_GRAM8_MAP", None)
     for mode in sorted({v[0] for v in variants}):
         Gm, _ = engine.gram(X, None, [0, ns], shift, mode=mode)

@@ -5,7 +5,8 @@ order.
 The header is plain C++ shared by the kernels and the host, so this test
 compiles it alone with g++ under AddressSanitizer + UBSan (host sanitizers
 only) next to an independent copy of the one-item-per-workgroup formulas (the
-XCD remap and the nested band walk as k_gram8w had them inline) and enumerates
+XCD remap and the nested band walk as the first one-item kernel had them
+inline) and enumerates
 every combination of
 
     nt ∈ {1, 2, 3, 4, 16} × chunks ∈ {1, 2, 7, 8, 9, 218} × CUs ∈ {8, 24, 256, 304} × chunk0 ∈ {0, 5}
