@@ -1046,6 +1046,41 @@ int ocm_sphere_rows_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t
 int ocm_sphere_rows_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t n, int32_t p,
                         const double* center, double* U, int64_t ldu, double* dist_out, void* stream);
 
+/* ---- cross-validation of the PCA itself: PRESS of every number of components ----
+ * Element-wise k-fold cross-validation (Bro, Kjeldahl, Smilde, Kiers 2008): for a model (μ, P) fitted
+ * without the rows given here, with y = x − μ, t = P·y, the residual r⁽ᵏ⁾ = y − Σ_{a≤k} t_a·P_a and the
+ * leverage h_j⁽ᵏ⁾ = Σ_{a≤k} P_aj² (r⁽⁰⁾ = y, h⁽⁰⁾ = 0), variable j predicted from the other p − 1
+ * variables through the loadings misses by exactly r_j⁽ᵏ⁾/(1 − h_j⁽ᵏ⁾), so
+ *   press_out[k] = Σ_rows Σ_j (r_j⁽ᵏ⁾/(1 − h_j⁽ᵏ⁾))²      k = 0..K
+ *   naive_out[k] = Σ_rows Σ_j (r_j⁽ᵏ⁾)²                   the row-wise curve (Σ Q at k components)
+ * Degenerate rule: where 1 − h_j⁽ᵏ⁾ ≤ 1e-8 the model reproduces variable j by itself and its leave-out
+ *   prediction is undefined: the variable is left out of press_out[k] (weight 0; naive_out keeps it)
+ *   and counted in ndegen_out[k].
+ * X [dev] with row pitch ldx ≥ p; rows [dev, nullable] m int64 row indices (NULL: rows 0..m − 1, not
+ *   checked); P [dev] K×p doubles with orthonormal rows, mu [dev] p doubles; press_out [dev] K + 1
+ *   doubles; naive_out [dev, nullable] K + 1 doubles; ndegen_out [dev, nullable] K + 1 int32.
+ * 1 ≤ K ≤ min(p, 64), p ≥ 2, m ≥ 0 (m = 0 writes zeros; ndegen_out is still filled), OCM_ERR_ARG
+ *   otherwise.  No alignment requirement (16-byte loads where p, ldx and the base allow them).
+ * One read of the rows: a tile of 16 centred rows waits in LDS between the projection and the residual
+ *   updates where 16·p elements fit once per resident workgroup (float32, two workgroups per CU:
+ *   p ≤ 1088 / 896 / 768 / 576 at K ≤ 16 / 32 / 48 / 64; float64, one per CU: p ≤ 1152 / 1088 / 960 /
+ *   896); wider rows are read a second time, out of L2.  f32: t on f32 MFMA over ≤ 64 columns per chain
+ *   flushed to f64, the residual explicit in f32 (r ← r − t_k·P_k); f64: fp64 MFMA and fp64 residual.
+ *   The weights 1/(1 − h)² are formed in fp64.  In float32 a variable with h_j close to 1 is
+ *   ill-conditioned short of the degenerate rule: the relative error of its term grows like
+ *   2⁻²⁴·|y_j|/|r_j|; give such data as float64.
+ * Sums: a lane adds its 64-column block sums in the element type, over one tile or (float32, K ≤ 32)
+ *   over the tiles of its chunk up to 128 block sums; then fp64: wave, workgroup, the tiles of a chunk
+ *   of 256 rows (at multiples of 256) in tile order, then the chunks in chunk order.  No atomics, no
+ *   workgroup waits for another: two launches on one input give the same bits.  Workspace:
+ *   (K + 1)·p weights, (f32) K·p + p floats, chunks·2·(K + 1) doubles. */
+int ocm_press_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                  const double* P, const double* mu, int32_t K, double* press_out, double* naive_out,
+                  int32_t* ndegen_out, void* stream);
+int ocm_press_f64(ocm_ctx* ctx, const double* X, int64_t ldx, const int64_t* rows, int64_t m, int32_t p,
+                  const double* P, const double* mu, int32_t K, double* press_out, double* naive_out,
+                  int32_t* ndegen_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

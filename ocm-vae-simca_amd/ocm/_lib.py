@@ -242,6 +242,10 @@ SIGNATURES = {
     "ocm_score_f32_diag_prep": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
                                         ctypes.POINTER(OcmDecision), c_void_p, c_i64, c_void_p, c_void_p]),
+    "ocm_press_f32": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                              c_void_p, c_void_p, c_void_p]),
+    "ocm_press_f64": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                              c_void_p, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 12  # include/ocm.h OCM_ABI_VERSION

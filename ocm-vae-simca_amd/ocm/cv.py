@@ -52,7 +52,7 @@ import torch.distributed as dist
 from . import engine, limits
 from .replica import replicated_group
 
-__all__ = ["grid", "cv_grid", "FoldModels"]
+__all__ = ["grid", "cv_grid", "FoldModels", "fold_models"]
 
 
 class _Spec:
@@ -204,53 +204,21 @@ def _rates(TP, TN, FP, FN):
     return sens, spec
 
 
-def cv_grid(X, y, folds, cls_idx, lv_values, combos, base_params, class_index, store_predictions,
-            row_offset=0, group=None, objects=None):
-    """The fold engine.  X: this rank's rows (host array or device tensor) =
-    global rows [row_offset, row_offset + len(X)); y, folds, cls_idx: global.
-    Returns (records, by_combo) in the reference's record order.
-
-    ``objects`` (an ``ocm.objectcv.ObjectTables``, single process only): every
-    fold's test rows are also reduced to per-object votes and decision sums
-    for all configurations (``ocm_cv_objects`` on the scores ``ocm_cv_counts``
-    reads) and handed to ``objects.add_fold``; the folds must be unions of
-    whole objects."""
-    if objects is not None and (group is not None or row_offset != 0):
-        raise ValueError("cv_grid: the object tables are per-process (no group, row_offset = 0)")
-    Xd = engine.as_device_f32(X)
+def fold_models(Xd, folds, loc_folds, n_target, lvmax, theta_mode, group=None):
+    """Pass 1 of the fold engine and the per-fold eigen-models at ``lvmax``:
+    one segmented Gram pass over the target rows (segments = folds), fold f's
+    training covariance by fp64 downdating, one eigensolve per fold.  Xd: this
+    rank's rows on the device (float32, float64 or a lazy view); folds: the
+    global row indices of every fold; loc_folds: the same as local indices of
+    Xd; n_target: the number of target rows over all ranks.  Returns the
+    ``FoldModels`` (on every rank of ``group``)."""
     dev = Xd.device
-    n_loc, p = Xd.shape
-    lo, hi = row_offset, row_offset + n_loc
-    y = np.asarray(y)
-    n_glob = y.shape[0]
-    # cross-rank only when a group is passed explicitly (``grid`` passes WORLD
-    # under torchrun); an initialised process group alone changes nothing
+    p = Xd.shape[1]
+    K = len(folds)
     distributed = group is not None
     W = dist.get_world_size(group) if distributed else 1
     R = dist.get_rank(group) if distributed else 0
-    K = len(folds)
-    lvs = sorted(set(int(v) for v in lv_values))
-    lvmax = lvs[-1]
-    n_target = int(cls_idx.size)
-    # the reference fits each fold's SIMCA on its training rows of the class, LV
-    # by LV in the grid's order, fold by fold (utils/CVSIMCA.py:158-185): the
-    # first LV above min(n_train, p) raises sklearn's ValueError there
-    from utils.SIMCA import check_components
-
-    for lv in lv_values:
-        for f_ in folds:
-            n_tr = n_target - int(f_.size)
-            check_components(int(lv), n_tr, p)
-    specs = [_Spec(dict(base_params, **c)) for c in combos]
-    theta_mode = max(limits.theta_mode_for(s) for s in specs)
-    need_train = any(s.needs_train_stats() for s in specs)
-    need_pct = any(s.needs_percentile() for s in specs)
-    others = np.setdiff1d(np.arange(n_glob), cls_idx)
-    positive_glob = (y == np.asarray(class_index)) if np.ndim(class_index) else (y == class_index)
-    positive_glob = np.asarray(positive_glob, dtype=bool).reshape(n_glob)
-
     # ---- pass 1: per-fold Grams of the target rows (one HBM pass) ----
-    loc_folds = [_local(f, lo, hi) for f in folds]
     order = np.concatenate(loc_folds) if loc_folds else np.zeros(0, np.int64)
     seg = np.concatenate([[0], np.cumsum([f.size for f in loc_folds])]).astype(np.int64)
     rows_t = torch.from_numpy(order).to(dev)
@@ -348,6 +316,56 @@ def cv_grid(X, y, folds, cls_idx, lv_values, combos, base_params, class_index, s
         models.theta_h.append(host[lvmax:lvmax + 3])
         models.n_train.append(n_tr)
     del G, cs, Gt, packs
+    return models
+
+
+def cv_grid(X, y, folds, cls_idx, lv_values, combos, base_params, class_index, store_predictions,
+            row_offset=0, group=None, objects=None):
+    """The fold engine.  X: this rank's rows (host array or device tensor) =
+    global rows [row_offset, row_offset + len(X)); y, folds, cls_idx: global.
+    Returns (records, by_combo) in the reference's record order.
+
+    ``objects`` (an ``ocm.objectcv.ObjectTables``, single process only): every
+    fold's test rows are also reduced to per-object votes and decision sums
+    for all configurations (``ocm_cv_objects`` on the scores ``ocm_cv_counts``
+    reads) and handed to ``objects.add_fold``; the folds must be unions of
+    whole objects."""
+    if objects is not None and (group is not None or row_offset != 0):
+        raise ValueError("cv_grid: the object tables are per-process (no group, row_offset = 0)")
+    Xd = engine.as_device_f32(X)
+    dev = Xd.device
+    n_loc, p = Xd.shape
+    lo, hi = row_offset, row_offset + n_loc
+    y = np.asarray(y)
+    n_glob = y.shape[0]
+    # cross-rank only when a group is passed explicitly (``grid`` passes WORLD
+    # under torchrun); an initialised process group alone changes nothing
+    distributed = group is not None
+    W = dist.get_world_size(group) if distributed else 1
+    R = dist.get_rank(group) if distributed else 0
+    K = len(folds)
+    lvs = sorted(set(int(v) for v in lv_values))
+    lvmax = lvs[-1]
+    n_target = int(cls_idx.size)
+    # the reference fits each fold's SIMCA on its training rows of the class, LV
+    # by LV in the grid's order, fold by fold (utils/CVSIMCA.py:158-185): the
+    # first LV above min(n_train, p) raises sklearn's ValueError there
+    from utils.SIMCA import check_components
+
+    for lv in lv_values:
+        for f_ in folds:
+            n_tr = n_target - int(f_.size)
+            check_components(int(lv), n_tr, p)
+    specs = [_Spec(dict(base_params, **c)) for c in combos]
+    theta_mode = max(limits.theta_mode_for(s) for s in specs)
+    need_train = any(s.needs_train_stats() for s in specs)
+    need_pct = any(s.needs_percentile() for s in specs)
+    others = np.setdiff1d(np.arange(n_glob), cls_idx)
+    positive_glob = (y == np.asarray(class_index)) if np.ndim(class_index) else (y == class_index)
+    positive_glob = np.asarray(positive_glob, dtype=bool).reshape(n_glob)
+
+    loc_folds = [_local(f, lo, hi) for f in folds]
+    models = fold_models(Xd, folds, loc_folds, n_target, lvmax, theta_mode, group)
 
     # ---- per-fold scoring, limits, counts ----
     ncfg = len(combos) * len(lvs)

@@ -406,6 +406,30 @@ def contributions(X, rows: torch.Tensor | None, m: int, P64: torch.Tensor, mean6
     return {"E": E, "C": C, "T2": T2, "Q": Q, "profiles": prof}
 
 
+def press(X, rows: torch.Tensor | None, m: int, P64: torch.Tensor, mean64: torch.Tensor):
+    """Element-wise cross-validation sums of the processed rows against a model
+    fitted without them (ocm_press_f32 / _f64): ``press`` (K + 1,) float64,
+    PRESS_k = Σ_rows Σ_j (r_j⁽ᵏ⁾/(1 − h_j⁽ᵏ⁾))² for k = 0..K components of P64
+    (K, p), ``naive`` (K + 1,) = Σ_rows Σ_j (r_j⁽ᵏ⁾)², and ``ndegen`` (K + 1,)
+    int32: the variables left out of PRESS_k because 1 − h_j⁽ᵏ⁾ ≤ 1e-8.  One read
+    of the rows.  A lazy ``PrepView`` is materialised first (ocm_prep_apply_f32),
+    as ``score`` does for a general quadratic form.  Returns device tensors."""
+    X = _plain(X)
+    if isinstance(X, PrepView):
+        X, rows = X.materialize(rows), None
+    K, p = P64.shape
+    dev = X.device
+    P64, mean64 = P64.contiguous(), mean64.contiguous()
+    out = torch.empty(K + 1, dtype=torch.float64, device=dev)
+    naive = torch.empty(K + 1, dtype=torch.float64, device=dev)
+    ndegen = torch.empty(K + 1, dtype=torch.int32, device=dev)
+    fn = "ocm_press_f64" if X.dtype == torch.float64 else "ocm_press_f32"
+    check(getattr(_lib.load(), fn)(Context.get(dev.index).handle, ptr(X), X.stride(0), ptr(rows), m, p,
+                                   ptr(P64), ptr(mean64), K, ptr(out), ptr(naive),
+                                   ptr(ndegen), _stream(dev)), fn)
+    return out, naive, ndegen
+
+
 def segment_sums(X, offsets, checked: bool = False) -> torch.Tensor:
     """(G, p) float64 device tensor of the column sums of rows
     [offsets[g], offsets[g + 1]) of X (ocm_segsum_f32 / _f64: one read of X, fp64

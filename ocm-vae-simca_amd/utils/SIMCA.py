@@ -468,6 +468,39 @@ class SIMCA(BaseEstimator, ClassifierMixin):
                for i, c in self._roc_classes(cls, "roc_points")}
         return out[cls] if cls is not None else out
 
+    def press(self, X, y=None, cls=None, max_components=None, cv=5, **kw):
+        """Cross-validate the PCA of one class for 0..max_components components
+        (``ocm.pcacv.pca_press``: element-wise k-fold PRESS, which needs rows of
+        the target class only).  ``y`` None: every row of X is the class;
+        otherwise the rows with ``y == cls`` (``cls`` default: the estimator's
+        single ``model_class``).  ``max_components`` default: ``maxPC``, at most
+        min(p, 64).  Needs no fitted model and changes none.  Returns a
+        ``PcaCvResult``; ``.select()`` names the number of components."""
+        from ocm import pcacv
+
+        p = int(X.shape[1])
+        if max_components is None:
+            max_components = min(int(self.maxPC), p, 64)
+        if not isinstance(cv, (int, np.integer)):  # a splitter names the target rows itself
+            return pcacv.pca_press(X, max_components, cv=cv, y=y, **kw)
+        rows = None
+        if y is not None:
+            lab = _host_labels(y)
+            if lab.shape != (int(X.shape[0]),):
+                raise ValueError(f"press: y has shape {lab.shape}, X has {int(X.shape[0])} rows")
+            if cls is None:
+                mc = self.model_class
+                mc = [mc] if isinstance(mc, (int, np.integer)) else (None if mc is None else list(np.ravel(mc)))
+                if mc is None or len(mc) != 1:
+                    raise ValueError("press: name the class whose PCA is cross-validated (cls=...)")
+                cls = mc[0]
+            rows = np.flatnonzero(lab == cls)
+            if rows.size == 0:
+                raise ValueError(f"press: no row of y has the label {cls!r}")
+        elif cls is not None:
+            raise ValueError("press: cls= needs y")
+        return pcacv.pca_press(X, max_components, cv=cv, rows=rows, **kw)
+
     def contributions(self, X, cls=None, groups=None, matrices=False):
         """Contribution plots of class ``cls`` (default: the only class) for the
         rows of X, extending utils/SIMCA.py:67-71: the residual
