@@ -118,7 +118,21 @@ int ocm_gram_f32(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows,
  *   OCM_GRAM_BF16X3 exact three-level bf16 split on bf16 MFMA;
  *   OCM_GRAM_I8X3_K32 the i8×3 Gram on v_mfma_i32_32x32x32_i8 (round 2's
  *                   kernel) instead of the default's 16x16x64: bit-identical
- *                   result, kept for kernel A/B. */
+ *                   result, kept for kernel A/B.
+ * chunk_rows, i8×3 modes (rows are cut into chunks; each chunk's f32 partial
+ * Gram is summed with the others in f64, in chunk order):
+ *   > 0  uniform chunks of that many rows, rounded up to whole 1536-row scale
+ *        blocks;
+ *   < 0  −chunk_rows balanced chunks: the B = ⌈n/1536⌉ scale blocks in that
+ *        many chunks (at most B) of ⌊B/N⌋ or ⌈B/N⌉ blocks, the longer ones
+ *        first.  One segment of contiguous rows only; with several segments
+ *        or a row list it is the automatic choice;
+ *   = 0  automatic: for one segment of contiguous rows a cost model picks a
+ *        balanced count with at most 12 blocks per chunk (csrc/ocm_gram_map.h
+ *        plan_chunks), otherwise — and whenever the model finds nothing
+ *        cheaper — uniform chunks of ≤ 4608 rows that fill the chip.
+ * G does not depend on the chunking beyond its f32 rounding; a given
+ * chunk_rows gives the same bits in both i8×3 modes. */
 #define OCM_GRAM_I8X3 0
 #define OCM_GRAM_F32 1
 #define OCM_GRAM_BF16X3 2

@@ -47,6 +47,9 @@ struct SegTable {
   int32_t cprefix[MAXSEG + 1]; // cumulative chunk counts
   int32_t nseg;
   int32_t chunk_rows;
+  // i8×3 Gram kernels only, bal_q > 0: one segment in balanced chunks (ocm_gram_map.h
+  // bal_first / bal_count) over block-major digit planes; chunk_rows is unused
+  int32_t bal_q, bal_r;
 };
 
 __device__ __forceinline__ void tile_coords(int t, int nt, int& ti, int& tj) {
@@ -745,7 +748,27 @@ struct Q8Plan {
   uint32_t* nmark;   // number of (row, column group) marks
 };
 
-constexpr float Q8TAU = 16.f;     // outlier threshold in robust column scales (2^e ≥ median|y|)
+// A chunk as the Gram kernels see it: its first scale block in the digit
+// planes / scale rows, its block count and its row count.  Uniform chunks
+// (several segments, gather lists): chunk-major planes of chunk_rows / Q8BLK
+// blocks per chunk.  Balanced chunks (st.bal_q > 0): block-major planes.
+__device__ __forceinline__ void q8_chunk_blocks(const SegTable& st, int chunk, size_t& fb, int& nb, int64_t& nrows) {
+  if (st.bal_q > 0) {
+    fb = (size_t)ocm_g8::bal_first(st.bal_q, st.bal_r, chunk);
+    nb = ocm_g8::bal_count(st.bal_q, st.bal_r, chunk);
+    nrows = (int64_t)nb * Q8BLK;
+    return;
+  }
+  int s = 0;
+  while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
+  const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
+  const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
+  fb = (size_t)chunk * (st.chunk_rows / Q8BLK);
+  nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
+  nrows = r1 - r0;
+}
+
+constexpr float Q8TAU = 16.f;    // outlier threshold in robust column scales (2^e ≥ median|y|)
 constexpr int Q8GROUP = 32;       // columns per guard group (= quantiser workgroup width)
 
 __device__ __forceinline__ uint32_t q8_byte(float a, int u) { return ((uint32_t)(int)a & 0xffu) << (8 * u); }
@@ -1580,15 +1603,14 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
   }
   const int tile = ti * nt - ti * (ti - 1) / 2 + (tj - ti);  // triangle index (the reduce's layout)
   const int I = ti * Q8T, J = tj * Q8T;
-  int s = 0;
-  while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
-  const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
-  const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
-  const int nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
+  size_t fb;
+  int nb;
+  int64_t nrows;
+  q8_chunk_blocks(st, chunk, fb, nb, nrows);
   // whole scale blocks (the loop body is one block of 24 stages); the
   // quantiser zero-fills every block of a chunk
   const int nstage3 = nb * Q8SPB;
-  const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
+  const size_t gbase = fb * Q8SPB;
 
   const int lane = threadIdx.x & 63;
   const int l31 = lane & 31, h = lane >> 5;
@@ -1604,8 +1626,8 @@ __global__ __launch_bounds__(256, 1) void k_gram8d(Q8Plan q, SegTable st, int nt
                                                0x00020000);
   }
   const int voff = l31 * 32 + h * 16;
-  const float* srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I + wm * 64 + lane;
-  const float* scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J + wn * 64 + lane;
+  const float* srow = q.scale + fb * q.P8 + I + wm * 64 + lane;
+  const float* scol = q.scale + fb * q.P8 + J + wn * 64 + lane;
 
 #define Q8D_LOAD(FA, FB, STG)                                                                         \
   do {                                                                                              \
@@ -1868,14 +1890,12 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
     }
     const int tile = ocm_g8::tile_index(nt, k.ti, k.tj);
     const int I = k.ti * Q8T + k.wm * 64, J = k.tj * Q8T + k.wn * 64;
-    int s = 0;
-    while (s + 1 < st.nseg && chunk >= st.cprefix[s + 1]) ++s;
-    const int64_t r0 = st.begin[s] + (int64_t)(chunk - st.cprefix[s]) * st.chunk_rows;
-    const int64_t r1 = min(r0 + (int64_t)st.chunk_rows, st.begin[s + 1]);
     Item it;
-    it.nb = (int)((r1 - r0 + Q8BLK - 1) / Q8BLK);
-    it.nvs = SKIP ? (int)((r1 - r0 + 63) / 64) : it.nb * SPB;  // stages holding rows (the rest are zero digits)
-    const size_t gbase = (size_t)chunk * (st.chunk_rows / Q8K);
+    size_t fb;
+    int64_t nrows;
+    q8_chunk_blocks(st, chunk, fb, it.nb, nrows);
+    it.nvs = SKIP ? (int)((nrows + 63) / 64) : it.nb * SPB;  // stages holding rows (the rest are zero digits)
+    const size_t gbase = fb * Q8SPB;
     const uint32_t span = (uint32_t)((size_t)it.nb * Q8SPB * gstride);
     const char* cbase = q.digits + gbase * gstride;
 #pragma unroll
@@ -1883,8 +1903,8 @@ __global__ __launch_bounds__(256, 1) void k_gram8e(Q8Plan q, SegTable st, int nt
       it.ra[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)I * 32), 0, span, 0x00020000);
       it.rb[dg] = __builtin_amdgcn_make_buffer_rsrc((void*)(cbase + dg * q.plane + (size_t)J * 32), 0, span, 0x00020000);
     }
-    it.srow = q.scale + (size_t)chunk * q.nblk * q.P8 + I;
-    it.scol = q.scale + (size_t)chunk * q.nblk * q.P8 + J;
+    it.srow = q.scale + fb * q.P8 + I;
+    it.scol = q.scale + fb * q.P8 + J;
     float* out = part + ((size_t)chunk * ntiles + tile) * (Q8T * Q8T) + k.wm * 64 * Q8T + k.wn * 64;
     it.rout = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, k.dead ? 0u : OUT_SPAN, 0x00020000);
     return it;
@@ -2177,11 +2197,31 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   const int P8 = (int)ocm::align_up((size_t)p, Q8T);
   const int nt = P8 / Q8T;
   const int ntiles = nt * (nt + 1) / 2;
+  const int nblocks = 4 * ntiles - nt, nwg = (nblocks + 3) / 4;
+  // Chunking.  chunk_rows > 0: uniform chunks of that many rows (whole scale
+  // blocks).  One segment of contiguous rows can instead be cut into `nbal`
+  // balanced chunks (ocm_gram_map.h): chunk_rows < 0 asks for −chunk_rows of
+  // them, chunk_rows == 0 for the planner's count — or, when the planner finds
+  // nothing modelled cheaper, and always with several segments or a gather
+  // list, the uniform automatic choice.
+  const int64_t B = (n + Q8BLK - 1) / Q8BLK;
+  const bool can_balance = nseg == 1 && !rows && !tr_O && B > 0 && B * Q8BLK < (1LL << 31);
+  int nbal = 0;
+  if (chunk_rows < 0 && can_balance) nbal = (int)std::min<int64_t>(-chunk_rows, B);
   if (chunk_rows <= 0) {
+    const bool planned = chunk_rows == 0 && can_balance;
     // enough workgroups to fill the chip (≥ 4 per CU), ≤ 4096 rows per chunk
     const int64_t want = std::max<int64_t>(1, (4LL * ctx->num_cus + ntiles - 1) / ntiles);
     chunk_rows = std::min<int64_t>(4096, (n + want - 1) / want);
+    if (planned) {
+      const int cb = (int)(std::max<int64_t>(Q8BLK, (int64_t)ocm::align_up((size_t)chunk_rows, Q8BLK)) / Q8BLK);
+      nbal = ctx->gram_plans.lookup((int)B, cb, nwg, ntiles, ctx->num_cus);
+    }
   }
+  // balanced: the quantiser and the column sums see ONE chunk of all B blocks
+  // (block-major digit planes, scales and column sums, no padded block); only
+  // the Gram kernels and the reduce see the nbal chunks
+  if (nbal > 0) chunk_rows = B * Q8BLK;
   // whole scale blocks (the Gram kernels' loop body)
   chunk_rows = std::max<int64_t>(Q8BLK, (int64_t)ocm::align_up((size_t)chunk_rows, Q8BLK));
   std::vector<int32_t> cprefix(nseg + 1, 0);
@@ -2194,7 +2234,7 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   const size_t plane = (size_t)nchunks * chunk_rows * P8;  // 1 B per digit
   const size_t scale_elems = (size_t)nchunks * nblk * P8;
   const size_t col_elems = (size_t)nchunks * nblk * P8;  // per scale block
-  const size_t part_elems = (size_t)nchunks * ntiles * Q8T * Q8T;
+  const size_t part_elems = (size_t)(nbal > 0 ? nbal : nchunks) * ntiles * Q8T * Q8T;
   // guard buffers
   const int ngrp = P8 / Q8GROUP, fw = (ngrp + 31) / 32;
   const int64_t nsamp = std::min<int64_t>(n, 4096);
@@ -2251,7 +2291,8 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     }
     const int64_t gchunks = cprefix[s1] - cprefix[s0];
     if (gchunks == 0) continue;
-    OCM_REQUIRE(gchunks * ntiles < (1LL << 31) && gchunks < 65536 * 1024LL, "ocm_gram_f32: too many workgroups");
+    OCM_REQUIRE(gchunks * ntiles < (1LL << 31) && gchunks < 65536 * 1024LL && (int64_t)nbal * ntiles < (1LL << 31),
+                "ocm_gram_f32: too many workgroups");
     tabs.push_back(tab);
     tab_s0.push_back(s0);
   }
@@ -2277,7 +2318,6 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
 #ifdef OCM_EXP_SELECTORS
   if (const char* mv = getenv("OCM_GRAM8_MAP")) gmap = !strcmp(mv, "round") ? ocm_g8::MAP_ROUND : ocm_g8::MAP_RANGE;
 #endif
-  const int nblocks = 4 * ntiles - nt, nwg = (nblocks + 3) / 4;
   auto tab_chunks = [&](size_t t) { return (int64_t)(cprefix[tab_s0[t] + tabs[t].nseg] - cprefix[tab_s0[t]]); };
 
   // all quantiser launches first, then the mark count is read back while the
@@ -2323,19 +2363,24 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
   // workgroup, the bit-for-bit reference on the 32×32×32 MFMA.
   for (size_t t = 0; t < tabs.size(); ++t) {
     const int s0 = tab_s0[t];
-    const int total = (int)(tab_chunks(t) * nwg);
+    const int total = (int)((nbal > 0 ? nbal : tab_chunks(t)) * nwg);
     const Q8Plan q = plan_for(s0);
+    SegTable gtab = tabs[t];
+    if (nbal > 0) {
+      gtab.bal_q = (int32_t)(B / nbal);
+      gtab.bal_r = (int32_t)(B % nbal);
+    }
     float* pg = part + (size_t)cprefix[s0] * ntiles * Q8T * Q8T;
     ocm::TimedRegion tr(ctx, OCM_KERNEL_GRAM, st, !unguarded);
-    const dim3 pgrid((unsigned)std::min(total, std::max(ctx->num_cus, ocm_g8::NXCD)));
+    const dim3 pgrid((unsigned)ocm_g8::launch_grid(total, ctx->num_cus));
     if (k32)
-      hipLaunchKernelGGL(k_gram8d, dim3((unsigned)total), dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks,
+      hipLaunchKernelGGL(k_gram8d, dim3((unsigned)total), dim3(256), 0, st, q, gtab, nt, ntiles, total, nwg, nblocks,
                          pg);
     else if (tr_O)
-      hipLaunchKernelGGL(k_gram8e<true>, pgrid, dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks, pg, 0,
+      hipLaunchKernelGGL(k_gram8e<true>, pgrid, dim3(256), 0, st, q, gtab, nt, ntiles, total, nwg, nblocks, pg, 0,
                          gmap);
     else
-      hipLaunchKernelGGL(k_gram8e<false>, pgrid, dim3(256), 0, st, q, tabs[t], nt, ntiles, total, nwg, nblocks, pg, 0,
+      hipLaunchKernelGGL(k_gram8e<false>, pgrid, dim3(256), 0, st, q, gtab, nt, ntiles, total, nwg, nblocks, pg, 0,
                          gmap);
   }
   OCM_CHECK_LAUNCH("k_gram8d/8e");
@@ -2367,8 +2412,8 @@ int gram_impl8(ocm_ctx* ctx, const float* X, int64_t ldx, const int64_t* rows, i
     }
     dim3 g((Q8T * Q8T / 4 + 255) / 256, ntiles);
     // colsum comes from k_colblk_sum (cmul = 0: the reduce skips it)
-    hipLaunchKernelGGL(k_gram_reduce<Q8T>, g, dim3(256), 0, st, part, colpart, nt, ntiles, p, cprefix[s],
-                       cprefix[s + 1], Gs, cs, 0);
+    hipLaunchKernelGGL(k_gram_reduce<Q8T>, g, dim3(256), 0, st, part, colpart, nt, ntiles, p,
+                       nbal > 0 ? 0 : cprefix[s], nbal > 0 ? nbal : cprefix[s + 1], Gs, cs, 0);
     hipLaunchKernelGGL(k_colblk_sum, dim3(P8 / 16), dim3(256), 0, st, colpart, (int64_t)cprefix[s] * nblk,
                        (int64_t)cprefix[s + 1] * nblk, P8, p, cs);
     OCM_CHECK_LAUNCH("k_colblk_sum");

@@ -160,4 +160,123 @@ OCM_MAP_HD Block block_tile(int nt, int ntiles, int nblocks, int local, int wave
 // index of tile (ti ≤ tj) in the partials' tile list
 OCM_MAP_HD int tile_index(int nt, int ti, int tj) { return ti * nt - ti * (ti - 1) / 2 + (tj - ti); }
 
+// ---------------------------------------------------------------------------
+// Balanced chunks.  One segment's B scale blocks split into N ≤ B chunks of
+// q + 1 (the first r chunks) or q blocks, q = B / N, r = B mod N: the longer
+// chunks are one run at the front, so only one round of the sweep mixes item
+// lengths.  The kernels derive a chunk's blocks from (q, r) alone.
+// ---------------------------------------------------------------------------
+OCM_MAP_HD int bal_first(int q, int r, int c) { return c * q + imin(c, r); }
+OCM_MAP_HD int bal_count(int q, int r, int c) { return q + (c < r ? 1 : 0); }
+
+// The planner (host).  A chunk's f32 running sum takes one flush per scale
+// block, so its rounding grows with the chunk's length: 12 blocks per chunk is
+// the cap the accuracy test is written for (4× the 3 blocks of the uniform
+// default) — a condition, not a tuning result.
+constexpr int PLAN_MAX_BLOCKS = 12;
+// The model's constants, all measured at 1M × 2048 on MI355X:
+//   PLAN_T_FIX_US  per item, entry → first MFMA (0.8 µs) plus last MFMA → end
+//                  (2.0 µs): k_gram8e's wall-clock stamps ("The
+//                  persistent Gram launch");
+//   PLAN_T_BLK_US  per item and scale block: the 3-block items' ≈ 80 µs less
+//                  the fixed part, over three (same stamps);
+//   PLAN_REDUCE_BYTES_PER_US  k_gram_reduce reading the f32 partials: 1.9 GB
+//                  in 0.30–0.38 ms (DESIGN kernel table).
+constexpr double PLAN_T_FIX_US = 2.8, PLAN_T_BLK_US = 25.7, PLAN_REDUCE_BYTES_PER_US = 5.9e6;
+// The model holds only while the digit panels a round has live stay in the
+// Infinity Cache (256 MiB): a round spans ⌈grid / nwg⌉ + 1 chunks, and an
+// item's panels are read again by the chunk's other items, partly a round
+// later.  Measured per-block time (profiles/r09a_gram_plan_ab.txt, three
+// chunks live of 9.4 MB per block): 25.5–25.7 µs for 3 … 7 blocks per chunk
+// (≤ 198 MB live), +0.6 % at 9 (255 MB), +3.7 % at 11 (311 MB), with the
+// bytes fetched beyond L2 up by a quarter; at 8 (226 MB) the kernel ran 0.5 %
+// under the 5 … 7-block plans and the whole call lost to them in the same
+// process.  Chunks whose round would fill more than PLAN_CACHE_FILL of the
+// cache are no candidates: three quarters admits 7 blocks at that shape.
+constexpr double PLAN_CACHE_BYTES = 256.0 * 1024 * 1024, PLAN_CACHE_FILL = 0.75;
+constexpr int PLAN_BLOCK_ROWS = 1536, PLAN_TILE_COLS = 128;  // the quantiser's scale block, the Gram's tile
+
+// the persistent launch's grid for `total` items on `cus` compute units
+OCM_MAP_HD int launch_grid(int total, int cus) { return imin(total, imax(cus, NXCD)); }
+
+// Modelled µs of Gram + reduce for `nl` chunks of `bl` blocks followed by `ns`
+// chunks of `bs` blocks (both the balanced split and the uniform one with its
+// short last chunk have this form): the makespan over the workgroups of
+// Σ (t_fix + blocks · t_blk) over the items round_slot hands each, plus the
+// reduce's pass over the partials (64 KiB per chunk and tile).
+inline double plan_cost(int nl, int bl, int ns, int bs, int nwg, int ntiles, int cus) {
+  const long long total_ll = (long long)(nl + ns) * nwg;
+  if (total_ll <= 0 || total_ll >= (1LL << 31)) return 1e300;
+  const int total = (int)total_ll, grid = launch_grid(total, cus);
+  const long long nlong_items = (long long)nl * nwg;
+  double span = 0.0;
+  for (int b = 0; b < grid; ++b) {
+    const Slot sl = round_slot(total, grid, b);
+    long long cl = sl.first < nlong_items ? (nlong_items - sl.first - 1) / grid + 1 : 0;
+    if (cl > sl.count) cl = sl.count;
+    const double t = sl.count * PLAN_T_FIX_US + PLAN_T_BLK_US * ((double)cl * bl + (double)(sl.count - cl) * bs);
+    if (t > span) span = t;
+  }
+  return span + (double)(nl + ns) * ntiles * 65536.0 / PLAN_REDUCE_BYTES_PER_US;
+}
+inline double plan_cost_balanced(int B, int N, int nwg, int ntiles, int cus) {
+  return plan_cost(B % N, B / N + 1, N - B % N, B / N, nwg, ntiles, cus);
+}
+// uniform chunks of cb blocks, the last one holding what is left
+inline double plan_cost_uniform(int B, int cb, int nwg, int ntiles, int cus) {
+  const int C = (B + cb - 1) / cb;
+  return plan_cost(C - 1, cb, 1, B - (C - 1) * cb, nwg, ntiles, cus);
+}
+
+// the longest chunk, in blocks, the planner may choose: the accuracy cap and
+// the cache condition (three digit planes of 1 B per value)
+inline int plan_max_blocks(int nwg, int ntiles, int cus) {
+  int nt = 1;
+  while (nt * (nt + 1) / 2 < ntiles) ++nt;
+  const double block_bytes = 3.0 * PLAN_BLOCK_ROWS * PLAN_TILE_COLS * nt;
+  const int live = (imax(cus, NXCD) + nwg - 1) / nwg + 1;
+  const double fit = PLAN_CACHE_BYTES * PLAN_CACHE_FILL / (live * block_bytes);
+  return fit >= PLAN_MAX_BLOCKS ? PLAN_MAX_BLOCKS : imax(1, (int)fit);
+}
+
+// The balanced chunk count for B scale blocks, or 0: keep the uniform plan of
+// `cb_uniform` blocks per chunk (the automatic choice before the planner),
+// which stands whenever no candidate is modelled strictly cheaper.  Candidates
+// are the N with ⌈B / N⌉ ≤ plan_max_blocks.
+inline int plan_chunks(int B, int cb_uniform, int nwg, int ntiles, int cus) {
+  if (B <= 3) return 0;  // at most one uniform chunk's worth: nothing to plan
+  double best = plan_cost_uniform(B, cb_uniform, nwg, ntiles, cus);
+  int bestN = 0;
+  const int maxb = plan_max_blocks(nwg, ntiles, cus);
+  for (int N = (B + maxb - 1) / maxb; N <= B; ++N) {
+    const double c = plan_cost_balanced(B, N, nwg, ntiles, cus);
+    if (c < best) {
+      best = c;
+      bestN = N;
+    }
+  }
+  return bestN;
+}
+
+// The planner's answers of one context, by (B, nwg, grid cap, uniform blocks):
+// a fit asks the same question every step and pays the model once.
+struct PlanMemo {
+  static constexpr int CAP = 16;
+  struct Entry {
+    int B, nwg, grid, cb, N;
+  };
+  Entry e[CAP];
+  int used = 0, next = 0;
+  int lookup(int B, int cb_uniform, int nwg, int ntiles, int cus) {
+    const int grid = imax(cus, NXCD);
+    for (int i = 0; i < used; ++i)
+      if (e[i].B == B && e[i].nwg == nwg && e[i].grid == grid && e[i].cb == cb_uniform) return e[i].N;
+    const int N = plan_chunks(B, cb_uniform, nwg, ntiles, cus);
+    e[next] = Entry{B, nwg, grid, cb_uniform, N};
+    next = (next + 1) % CAP;
+    if (used < CAP) ++used;
+    return N;
+  }
+};
+
 }  // namespace ocm_g8

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ocm.h"
+#include "ocm_gram_map.h"
 
 struct ocm_ctx {
   int device = 0;
@@ -21,6 +22,7 @@ struct ocm_ctx {
   size_t host_bytes = 0;
   int num_cus = 256;
   uint32_t last_gram_marks = 0;  // outlier-guard marks of the last i8×3 Gram (ocm_gram_last_marks)
+  ocm_g8::PlanMemo gram_plans;  // the i8×3 Gram's chunk planner, memoised (ocm_gram_map.h)
   int64_t prep_materialised = 0;  // lazy views written out by a fallback path (ocm_prep_materialised)
   // live kernel timing (ocm_ctx_set_timing): event pairs per timed kernel
   bool timing = false;

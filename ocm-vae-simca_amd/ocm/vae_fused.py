@@ -458,9 +458,12 @@ class _LinearPair(torch.autograd.Function):
 
 
 def _adjacent(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """[a; b] along dim 0: a view when b follows a in memory, else torch.cat."""
+    """[a; b] along dim 0: a view when b follows a in memory inside ONE storage
+    (two allocations that the caching allocator happened to place back to back
+    are no such pair: a view cannot reach past a's storage), else torch.cat."""
     if (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and a.shape[1:] == b.shape[1:]
-            and b.data_ptr() == a.data_ptr() + a.numel() * a.element_size()):
+            and b.data_ptr() == a.data_ptr() + a.numel() * a.element_size()
+            and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()):
         return torch.as_strided(a, (a.shape[0] + b.shape[0],) + tuple(a.shape[1:]), a.stride())
     return torch.cat([a, b])
 

@@ -6,7 +6,9 @@ of each mode against an fp64 Gram of a row sample.
 
     python scripts/bench_gram.py [--variants i8x3:0,f32:0,bf16x3:0,i8x3:0:range] [--outliers 0.005]
 
-A third field sets OCM_GRAM8_MAP for that variant (range | round: k_gram8e's
+The second field is chunk_rows as ocm_gram_f32_ex takes it: rows per uniform
+chunk, 0 for the automatic choice (the planner), or a negative count of
+balanced chunks (i8x3:-96 = 96 balanced chunks).  A third field sets OCM_GRAM8_MAP for that variant (range | round: k_gram8e's
 work map).  The selector is read by `make exp` libraries only (OCM_LIB=…,
 OCM_ALLOW_EXP_LIB=1).  "wall" is the whole call (guard, quantiser, Gram,
 reduce) between two device synchronisations.
@@ -26,7 +28,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--p", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--variants", default="i8x3:0,bf16x3:0,f32:0", help="mode:chunk_rows[:map] (0 = automatic)")
+    ap.add_argument("--variants", default="i8x3:0,bf16x3:0,f32:0", help="mode:chunk_rows[:map] (0 = automatic, -N = N balanced chunks)")
     ap.add_argument("--outliers", type=float, default=0.0, help="fraction of rows scaled x100..x1000")
     args = ap.parse_args()
     import torch
