@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ocm.h"
+#include "ocm_eig_plan.h"
 #include "ocm_gram_map.h"
 
 struct ocm_ctx {
@@ -80,13 +81,15 @@ void* host_staging(ocm_ctx* ctx, size_t bytes);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Buffers carved out of one allocation, each on a 256-byte boundary of it.  A
+// null base measures: every take returns null and `off` ends as the size.
 struct Carve {
   char* base;
   size_t off = 0;
   template <typename T>
   T* take(size_t count) {
     off = align_up(off, 256);
-    T* p = reinterpret_cast<T*>(base + off);
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += count * sizeof(T);
     return p;
   }
@@ -212,7 +215,7 @@ __device__ __forceinline__ bool last_arrival(unsigned* counter, unsigned n) {
 // sub-counter idx / 16 and the last of each sixteen counts in the main
 // counter: ≤ 16 + ⌈n/16⌉ adds in a row.  Counters of `slot` start at word
 // slot · tickets_per_slot(n) · TICKET_STRIDE, one per 128-B line.
-constexpr int TICKET_STRIDE = 32;
+using ocm_eig::TICKET_STRIDE;  // (ocm_eig_plan.h: the eigensolver's workspace plan counts in it)
 __host__ __device__ constexpr int tickets_per_slot(int n) { return 1 + (n + 15) / 16; }
 __device__ __forceinline__ bool last_arrival2(unsigned* tickets, int slot, unsigned n, unsigned idx) {
   __shared__ bool last_;

@@ -38,7 +38,12 @@ namespace {
 // tile0 (MODE 1): first upper-triangle tile of this launch (a rank's slice of
 // the trace GEMM when the θ3 work is split over GPUs).
 // ---------------------------------------------------------------------------
-constexpr int DT = 64, DBK = 16, DPAD = 16;
+using ocm_eig::CQ_G;  // the eigensolver's constants that its workspace plan shares (ocm_eig_plan.h)
+using ocm_eig::CVQ_G1;
+using ocm_eig::DT;
+using ocm_eig::JMAX;
+using ocm_eig::QB;
+constexpr int DBK = 16, DPAD = 16;
 #ifndef OCM_JACOBI_TOL2
 #define OCM_JACOBI_TOL2 1e-26  // Jacobi stop: off-diagonal ‖·‖² ≤ this × diagonal ‖·‖²
 #endif
@@ -477,7 +482,6 @@ __global__ __launch_bounds__(256) void k_atb_part(const double* __restrict__ A, 
 // each of the n-1 rounds every index is in exactly one rotation pair.
 // Outputs eigenvalues (descending) and Z (n_in×n_in, column j = eigenvector j).
 // ---------------------------------------------------------------------------
-constexpr int JMAX = 64;
 
 // NF > 0: compile-time padded size (index arithmetic folds); NT threads
 // (64 = one wave: the per-round barriers reduce to LDS waits).
@@ -978,7 +982,6 @@ __global__ __launch_bounds__(64) void k_trsm_rows(const double* __restrict__ W, 
 }
 
 // b = 32: the fused path's block width (its CholQR kernels are below)
-constexpr int QB = 32;
 // lane l's double, wave-uniform l (two v_readlane_b32 into SGPRs: no LDS round trip)
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   const uint64_t u = __builtin_bit_cast(uint64_t, v);
@@ -1018,7 +1021,6 @@ __device__ __forceinline__ double hash_normal(uint64_t a);
 // A = src[16rb + c][4ks + g], B = M[4ks + g][16cb + c] and yields
 // dst[16rb + g + 4r][16cb + c] in accumulator r.
 // ---------------------------------------------------------------------------
-constexpr int CQ_G = 16;  // workgroups per launch (a power of two: the ticket wraps)
 
 __device__ __forceinline__ void cq_blocks(int p, int& lo, int& hi) {
   const int nrb = (p + 15) / 16;
@@ -1042,18 +1044,6 @@ __device__ __forceinline__ void cq_apply_block(const double* src, int p, int rb,
   }
 }
 
-#ifdef OCM_CVQ_STAMPS  // make exp diagnostic: phase times of k_cvq32 (wall clock, 100 MHz)
-__device__ unsigned long long g_cvq_st[10];
-__device__ __forceinline__ void cvq_stamp(int slot, bool is_min) {
-  if (threadIdx.x == 0) {
-    const unsigned long long t = wall_clock64() + (unsigned long long)(threadIdx.x & 1);  // lane-dependent: a vector atomic
-    if (is_min) atomicMin(&g_cvq_st[slot], t); else atomicMax(&g_cvq_st[slot], t);
-  }
-}
-#define CVQ_STAMP(s_, m_) cvq_stamp(s_, m_)
-#else
-#define CVQ_STAMP(s_, m_)
-#endif
 // The CholQR factor of a 32×32 Gram S (in sS): column scaling r_i = 1/√S_ii,
 // S' = D S D = L Lᵀ by wave 0 in registers (lane i holds row i, v_readlane
 // broadcasts, pivot clamp 1e-14 as k_chol), X = L⁻¹ by back substitution and
@@ -1339,7 +1329,6 @@ __global__ __launch_bounds__(256) void k_cq_apply32(const double* __restrict__ s
 // Sin[1024] = 1: the previous launch met a zero column and factored (and
 // repaired W) itself; Min holds its factor.  defer_next: this launch leaves
 // its Gram in Sout (non-degenerate) instead of factoring it.
-constexpr int CVQ_G1 = 16;
 template <bool DEFER>
 __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int p, const double* __restrict__ Win,
                                              const double* __restrict__ Min, double* __restrict__ Wout,
@@ -1369,7 +1358,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
   const int kb = (half * PW + pwave) * kslice;
   const int ke = prod ? min(p, kb + kslice) : kb;  // waves 3 and 7 form no product
   const double* crow = C + (int64_t)min(r0 + i, p - 1) * p;
-  CVQ_STAMP(0, true);
   f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
   for (int k0 = kb; k0 < ke; k0 += 32) {
     double a[8], b0[8], b1[8];
@@ -1403,12 +1391,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
       red[pwave][(g + 4 * r) * 33 + i] = acc0[r];
       red[pwave][(g + 4 * r) * 33 + 16 + i] = acc1[r];
     }
-#ifdef OCM_CVQ_STAMPS
-    if (lane == 0) {
-      const unsigned long long t = wall_clock64() + (unsigned long long)(lane & 1);
-      atomicMax(&g_cvq_st[9], t);
-    }
-#endif
   }
   if (DEFER) {
     if (wave == 7) {  // the factor of Win: from the previous launch's Gram (or its own factor)
@@ -1428,18 +1410,11 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
         __builtin_amdgcn_wave_barrier();
         cq_factor_wave(sS, lsc, rsc, dinv, sm, lane);
       }
-#ifdef OCM_CVQ_STAMPS
-      if (lane == 0) {
-        const unsigned long long t = wall_clock64() + (unsigned long long)(lane & 1);
-        atomicMax(&g_cvq_st[8], t);
-      }
-#endif
     }
   } else if (Min) {
     for (int e = tid; e < 32 * 32; e += 512) sm[e >> 5][e & 31] = Min[e];
   }
   __syncthreads();
-  CVQ_STAMP(1, false);
   const int orow = tid >> 5, ocol = tid & 31;
   double v = 0.0;
 #pragma unroll
@@ -1460,7 +1435,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
   if (!last) return;
   const double o = part[(int64_t)(blockIdx.x ^ 1) * 512 + tid];
   double y = half == 0 ? v + o : o + v;  // (C·Win)[r0 + orow][ocol]
-  CVQ_STAMP(2, false);
   const bool rok = r0 + orow < p;
   if (DEFER || Min) {  // basis change on the output rows: (C·Win)·Min
     sv[orow][ocol] = y;
@@ -1484,7 +1458,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
     for (int r = 0; r < 16; ++r) gs = fma(sv[r][a], sv[r][b], gs);
     st_agent(&gpart[(int64_t)rb * 1024 + e], gs);
   }
-  CVQ_STAMP(3, false);
   const int ngrp = (nrb + CVQ_G1 - 1) / CVQ_G1;
   const int grp = rb / CVQ_G1, g0 = grp * CVQ_G1, gsize = min(CVQ_G1, nrb - g0);
   if (!last_arrival(gtick + (1 + grp) * TICKET_STRIDE, (unsigned)gsize)) return;
@@ -1500,9 +1473,7 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
     for (int q = 0; q < CVQ_G1; ++q) acc += pv[q];
     st_agent(&gsum[(int64_t)grp * 1024 + e], acc);
   }
-  CVQ_STAMP(4, false);
   if (!last_arrival(gtick, (unsigned)ngrp)) return;
-  CVQ_STAMP(5, false);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int e = tid + 512 * h;
@@ -1517,7 +1488,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
     sS[e >> 5][e & 31] = acc;
   }
   __syncthreads();
-  CVQ_STAMP(6, false);
   if (defer_next) {  // hand the Gram on (the next launch factors it) unless a column is zero
     if (tid == 0) degen = 0;
     __syncthreads();
@@ -1532,7 +1502,6 @@ __global__ __launch_bounds__(512) void k_cvq32(const double* __restrict__ C, int
   }
   cq_finalize(sS, rsc, &degen, Wout, p, 1, seed, Mout);
   __syncthreads();
-  CVQ_STAMP(7, false);
 }
 
 __device__ __forceinline__ double hash_normal(uint64_t a) {
@@ -2096,43 +2065,34 @@ int dgemm(const double* A, int64_t lda, const double* B, int64_t ldb, double* D,
   return OCM_OK;
 }
 
+#ifdef OCM_JACOBI_STAMPS  // make exp diagnostic (scripts/jacobi_micro.py, profiles/r06w_jacobi_round_probes.txt)
+// the phase times of the k_jacobi_1b launch last queued on st, printed once it is done; clears the stamps
+void jacobi_print_stamps(hipStream_t st, bool tested) {
+  static unsigned long long h[16][64];
+  (void)hipStreamSynchronize(st);
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_jac_st), sizeof(h));
+  fprintf(stderr, "jacobi32 us: load %.2f", (h[1][0] - h[0][0]) / 100.0);
+  for (int i = 1; i < 13 && h[i + 1][0] > h[i][0] && h[i][0] >= h[1][0]; ++i)
+    fprintf(stderr, " sweep%d %.2f", i - 1, (h[i + 1][0] - h[i][0]) / 100.0);
+  fprintf(stderr, " | rounds %.2f sort+write %.2f", (h[13][0] - h[1][0]) / 100.0, (h[14][0] - h[13][0]) / 100.0);
+  if (tested) fprintf(stderr, " test %.2f", (h[15][0] - h[14][0]) / 100.0);
+  fprintf(stderr, "\n");
+  static unsigned long long z[16][64];
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_jac_st), z, sizeof(z));
+}
+#else
+inline void jacobi_print_stamps(hipStream_t, bool) {}
+#endif
+
 int jacobi(const double* A, int n, int max_sweeps, double* ev, double* Z, hipStream_t st, const double* S = nullptr,
            const unsigned* sflag = nullptr, unsigned epoch = 0, int k = 0, double* res = nullptr,
            unsigned spins = OCM_JACOBI_WAIT_SPINS) {
   // n = 32: the one-barrier block kernel k_jacobi_1b (107 µs alone against 139 for the two-barrier
   // k_jacobi_blk, r05s3_jacobi_ab.txt; the block rounds in one wave without barriers measured 204 µs,
   // r05s_eig_timeline.txt); S: the Rayleigh–Ritz test at its end (S from k_rr_resid32 in flight)
-#ifdef OCM_JACOBI_SWEEPS  // make exp diagnostic: print the sweep count of each 32×32 solve
-  if (n == 32) {
-    static int* dsw = nullptr;
-    if (!dsw) (void)hipMalloc(reinterpret_cast<void**>(&dsw), sizeof(int));
-    hipLaunchKernelGGL(k_jacobi_1b<32>, dim3(1), dim3(320), 0, st, A, max_sweeps, ev, Z, dsw, S, sflag, epoch, k,
-                       res, spins);
-    int hsw = -1;
-    (void)hipMemcpyAsync(&hsw, dsw, sizeof(int), hipMemcpyDeviceToHost, st);
-    (void)hipStreamSynchronize(st);
-    fprintf(stderr, "jacobi32 sweeps %d\n", hsw);
-    return OCM_OK;
-  }
-#endif
   if (n == 32)
     hipLaunchKernelGGL(k_jacobi_1b<32>, dim3(1), dim3(320), 0, st, A, max_sweeps, ev, Z, nullptr, S, sflag, epoch, k,
                        res, spins);
-#ifdef OCM_JACOBI_STAMPS  // (scripts/jacobi_micro.py, profiles/r06w_jacobi_round_probes.txt)
-  if (n == 32) {
-    static unsigned long long h[16][64];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_jac_st), sizeof(h));
-    fprintf(stderr, "jacobi32 us: load %.2f", (h[1][0] - h[0][0]) / 100.0);
-    for (int i = 1; i < 13 && h[i + 1][0] > h[i][0] && h[i][0] >= h[1][0]; ++i)
-      fprintf(stderr, " sweep%d %.2f", i - 1, (h[i + 1][0] - h[i][0]) / 100.0);
-    fprintf(stderr, " | rounds %.2f sort+write %.2f", (h[13][0] - h[1][0]) / 100.0, (h[14][0] - h[13][0]) / 100.0);
-    if (S) fprintf(stderr, " test %.2f", (h[15][0] - h[14][0]) / 100.0);
-    fprintf(stderr, "\n");
-    static unsigned long long z[16][64];
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_jac_st), z, sizeof(z));
-  }
-#endif
   else if (n == 48)
     hipLaunchKernelGGL(k_jacobi_blk<48>, dim3(1), dim3(256), 0, st, A, max_sweeps, ev, Z, nullptr);
   else if (n == 64)
@@ -2142,6 +2102,7 @@ int jacobi(const double* A, int n, int max_sweeps, double* ev, double* Z, hipStr
   else
     hipLaunchKernelGGL((k_jacobi<0, 256>), dim3(1), dim3(256), 0, st, A, n, max_sweeps, ev, Z, nullptr);
   OCM_CHECK_LAUNCH("k_jacobi");
+  if (n == 32) jacobi_print_stamps(st, S != nullptr);
   return OCM_OK;
 }
 
@@ -2159,11 +2120,9 @@ int trsm_rows(const double* W, const double* L, int p, int b, double* V, hipStre
   // 64-thread workgroups: the p rows spread over p/64 CUs (the per-row chain is serial)
   dim3 g((p + 63) / 64);
   switch (b) {
-    case 16: hipLaunchKernelGGL(k_trsm_rows<16>, g, dim3(64), 0, st, W, L, p, V); break;
-    case 32: hipLaunchKernelGGL(k_trsm_rows<32>, g, dim3(64), 0, st, W, L, p, V); break;
     case 48: hipLaunchKernelGGL(k_trsm_rows<48>, g, dim3(64), 0, st, W, L, p, V); break;
     case 64: hipLaunchKernelGGL(k_trsm_rows<64>, g, dim3(64), 0, st, W, L, p, V); break;
-    default: return ocm::fail(OCM_ERR_UNSUPPORTED, "trsm block must be 16/32/48/64");
+    default: return ocm::fail(OCM_ERR_UNSUPPORTED, "trsm block must be 48 or 64");
   }
   OCM_CHECK_LAUNCH("k_trsm_rows");
   return OCM_OK;
@@ -2257,664 +2216,616 @@ int eig_side_init(ocm_ctx* ctx) {
   return OCM_OK;
 }
 
+// ---- ocm_eig_topk -----------------------------------------------------------
+// eig_topk_impl plans (ocm_eig_plan.h: the path, the block width b, the
+// workspace layout) and hands over to one driver per path: eig_small,
+// eig_fused32 (b = 32), eig_block (b = 48 / 64 on the device, wider blocks
+// with their b×b steps on the host).
+//
+// Iterations are plain orthogonal iterations V ← orth(C V) except at the
+// Rayleigh–Ritz steps, which are the only ones that can test convergence:
+// the subspace after iteration i is span(Cⁱ V₀) whatever rotations happen in
+// between, so Rayleigh–Ritz only has to run where the test can pass
+// (ocm_eig::Schedule predicts where).  The first test comes at iteration
+// PLAIN + 1: the spectra of the bench data (p = 2048, k = 20) converge at
+// iteration 5, the derivative spectra of the nuts preprocessing
+// (simca_nuts.py:47-52) at ~33.
+using ocm_eig::PLAIN;
+
+// what the drivers share: the call's arguments, the plan and the carved workspace
+struct EigState {
+  ocm_ctx* ctx;
+  hipStream_t st;
+  const double* C;
+  int p, k;
+  double tol;
+  int max_iter, theta_mode, slice, nslices;
+  double *evals_out, *evecs_out, *theta_out, *inv_out;
+  double rcond;
+  ocm_eig::Plan pl;
+  ocm_eig::Layout w;
+  double* hres;  // pinned: θ (b) then the residuals (b) of a test; wide: + b×b staging, a b×b result, b values
+  double* hmat() const { return hres + 2 * pl.b; }
+};
+
+int eig_small(const EigState& s) {
+  double *ev = s.w.theta, *Z = s.w.Z;
+  int rc = jacobi(s.C, s.p, 60, ev, Z, s.st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(64), 0, s.st, ev, Z, s.p, s.k, s.evals_out, s.evecs_out,
+                     s.theta_mode ? s.theta_out : nullptr);
+  OCM_CHECK_LAUNCH("k_small_finish");
+  if (s.inv_out) hipLaunchKernelGGL(k_inv_evals, dim3(1), dim3(256), 0, s.st, s.evals_out, s.k, s.rcond, s.inv_out);
+  if (s.theta_mode && s.slice != 0) OCM_HIP(hipMemsetAsync(s.theta_out + 2, 0, sizeof(double), s.st));
+  return OCM_OK;
+}
+
+// θ1..θ3 of (I − P)C(I − P), P the projector on the first kd columns of the
+// orthonormal block Vb (Wb_ = C·Vb, Hb = Vbᵀ Wb_): the rank-2kd deflation
+// GEMM with its trace and Frobenius epilogue → out3[0..1], and this slice's
+// θ3 rows → out3[2], all on stream sa; the θ3 Gram runs on gctx's workspaces.
+// s2 (≠ sa: the fused path's second side stream) takes the Δ terms beside the
+// θ3 Gram; eig_ev[4] / [5] order them.
+int theta_deflated(const EigState& s, const double* Vb, const double* Wb_, const double* Hb, int kd, hipStream_t sa,
+                   hipStream_t s2, ocm_ctx* gctx, double* out3) {
+  const int p = s.p, b = s.pl.b;
+  double *Ud = s.w.Ud, *Wd = s.w.Wd, *dpart = s.w.dpart;
+  hipLaunchKernelGGL(k_deflate_operands_h, dim3((unsigned)(((size_t)p * kd + 255) / 256)), dim3(256), 0, sa, Vb, Wb_,
+                     Hb, p, b, kd, Ud, Wd);
+  OCM_CHECK_LAUNCH("k_deflate_operands_h");
+  // the deflated matrix D = C − U·Wdᵀ is never stored in fp64: k_dgemm<3>
+  // writes its off-diagonal part O (float32, the θ3 Gram's input), its
+  // diagonal Δ, per-tile row sums of O² and the {tr D, ‖D‖²} partials.  O
+  // and the partials live in gctx's second arena (the Gram takes gctx's
+  // workspace).
+  const size_t pp = (size_t)p * p;
+  const int ntc = (p + DT - 1) / DT;
+  const int ntq = (p + 127) / 128;
+  const int ntr_cap = ntq * (ntq + 1) / 2 * 16;  // k_gram_trace partials
+  const size_t o32_bytes = (pp * sizeof(float) + 255) / 256 * 256;
+  char* aux = static_cast<char*>(ocm::workspace_aux(
+      gctx, o32_bytes + (2 * (size_t)p + (size_t)ntc * p + ntr_cap + 64) * sizeof(double), sa));
+  if (!aux) return OCM_ERR_NOMEM;
+  float* O32 = reinterpret_cast<float*>(aux);
+  double* diag = reinterpret_cast<double*>(aux + o32_bytes);
+  double* rowpart = diag + p;
+  double* dpart3 = rowpart + (size_t)ntc * p;  // ≤ p/256 + 1 workgroup partials
+  double* trpart = dpart3 + p;
+  const dim3 gd(ntc, ntc, 1);
+  if (2 * kd <= 64)
+    hipLaunchKernelGGL(k_deflate64, gd, dim3(256), 0, sa, Ud, (int64_t)(2 * kd), Wd, (int64_t)p, diag, p, p, 2 * kd,
+                       s.C, (int64_t)p, dpart, O32, rowpart);
+  else
+    hipLaunchKernelGGL(k_dgemm<3>, gd, dim3(256), 0, sa, Ud, (int64_t)(2 * kd), Wd, (int64_t)p, diag, (int64_t)p, p, p,
+                       2 * kd, 2 * kd, s.C, (int64_t)p, dpart, 0, O32, rowpart);
+  OCM_CHECK_LAUNCH("k_dgemm deflate");
+  // the tile pairs sit in this context's workspace, which the θ3 Gram takes
+  // over when gctx is this context (the unfused paths): sum them first there
+  const bool own_ws = gctx == s.ctx;
+  if (own_ws) {
+    hipLaunchKernelGGL(k_theta_final, dim3(1), dim3(256), 0, sa, dpart, (int)(gd.x * gd.y), nullptr, 0, nullptr, 0,
+                       out3, 1);
+    OCM_CHECK_LAUNCH("k_theta_final pairs");
+  }
+  // θ3 = Σ Δ³ + 3 Σ Δ_i Σ_j O_ij² + Σ O∘(O²): this slice's rows of the Δ
+  // terms (on s2), and the i8×3 Gram of its rows of O paired with all of O
+  // in the Gram's epilogue (k_gram_trace, on sa)
+  const int r0 = (int)((int64_t)p * s.slice / s.nslices), r1 = (int)((int64_t)p * (s.slice + 1) / s.nslices);
+  int nb3 = 0, ntr = 0;
+  if (s.theta_mode >= 2 && r1 > r0) {
+    const int nr = r1 - r0;
+    nb3 = (nr + 255) / 256;
+    if (s2 != sa) {
+      OCM_HIP(hipEventRecord(s.ctx->eig_ev[4], sa));
+      OCM_HIP(hipStreamWaitEvent(s2, s.ctx->eig_ev[4], 0));
+    }
+    hipLaunchKernelGGL(k_theta3_rows, dim3(nb3), dim3(256), 0, s2, diag, rowpart, ntc, p, r0, r1, dpart3);
+    OCM_CHECK_LAUNCH("k_theta3_rows");
+    if (s2 != sa) OCM_HIP(hipEventRecord(s.ctx->eig_ev[5], s2));
+    int rc2 = ocm::trace_gram_rows_i8(gctx, O32 + (size_t)r0 * p, p, nr, p, O32, trpart, &ntr, sa);
+    if (rc2) return rc2;
+    if (s2 != sa) OCM_HIP(hipStreamWaitEvent(sa, s.ctx->eig_ev[5], 0));
+  }
+  hipLaunchKernelGGL(k_theta_final, dim3(1), dim3(256), 0, sa, dpart, own_ws ? 0 : (int)(gd.x * gd.y), dpart3, nb3,
+                     trpart, ntr, out3, own_ws ? 2 : 3);
+  OCM_CHECK_LAUNCH("k_theta_final");
+  return OCM_OK;
+}
+
+// V₀: a Gaussian block, used as it is — the subspace after i iterations is
+// span(Cⁱ V₀) whatever basis V₀ has, so only the Rayleigh–Ritz steps need an
+// orthonormal basis (every iteration before one ends with CholQR2), and an
+// orthonormalisation of V₀ costs a CholQR pass (≈ 36 µs) for nothing.  The
+// launch also zeroes the tickets (ocm_eig::carve).  rr_first (max_iter = 1,
+// Rayleigh–Ritz on the first product): a second block into T1, which the
+// caller orthonormalises into V.
+int eig_start_block(const EigState& s, bool rr_first) {
+  const size_t pb = s.pl.pb;
+  hipLaunchKernelGGL(k_randn, dim3((unsigned)((std::max<size_t>(pb, s.pl.nzero_cv) + 255) / 256)), dim3(256), 0, s.st,
+                     s.w.V, (int64_t)pb, 0x5EEDull, s.w.cq_ticket, 1, s.w.cv_ticket, s.pl.nzero_cv);
+  OCM_CHECK_LAUNCH("k_randn");
+  if (rr_first) {
+    hipLaunchKernelGGL(k_randn, dim3((unsigned)((pb + 255) / 256)), dim3(256), 0, s.st, s.w.T1, (int64_t)pb, 0x5EEDull);
+    OCM_CHECK_LAUNCH("k_randn");
+  }
+  return OCM_OK;
+}
+
+// ---- b = 32: the fused path -------------------------------------------------
+// The chain of plain iterations: the current unnormalised block Wc and its
+// CholQR factor Mc (nullptr: Wc is orthonormal or the start block, used as it
+// is), the block the next launch writes, the factor slot it uses, and the
+// Gram the previous plain launch left unfactored (k_cvq32<true>).
+//
+// Chebyshev-filtered iterations, from the first failed
+// Rayleigh–Ritz test on: the test's Ritz values bound the unwanted spectrum
+// (λ_{b+1} … λ_p ≤ θ_b up to the test's accuracy; C is PSD, so ≥ 0), and a
+// degree-d Chebyshev polynomial T_d(X), X = 2C/θ_b − I, damps [0, θ_b] to
+// ≤ 1 while it amplifies λ_k by T_d(2λ_k/θ_b − 1) ≈ e^{d·acosh(2λ_k/θ_b − 1)}
+// — for a slow gap (λ_k/θ_b = 1 + δ) a rate of e^{−2√δ} per product against
+// (1 + δ)^{−1} for the plain iteration.  Each product is one three-term step
+// Y_{j+1} = (4/θ_b)·C·Y_j − 2Y_j − Y_{j−1} (k_cv32x) with no CholQR in
+// between; a segment ends with one CholQR factor once the block's condition
+// would pass ≈ 1e6 (T_d(x_1) ≤ 1e6, x_1 = 2θ_1/θ_b − 1), and the next segment
+// restarts the recurrence from the orthonormalised block.  Before the first
+// test nothing bounds λ_{b+1} (the bench data converge at that test), so the
+// plain iterations stay.
+struct Chain32 {
+  double* Wc;
+  double* Wn;
+  const double* Mc = nullptr;
+  int mslot = 0;
+  const double* Sprev = nullptr;
+  int sslot = 0;
+  bool cheb = false;       // filtered continuation active
+  bool y1_from_w = false;  // the segment starts at the Rayleigh–Ritz basis V with C·V = W in hand
+  double cheb_beta = 0.0;  // θ_b of the test that switched it on
+  int cheb_dmax = 1;
+};
+
+// one filter segment from iteration it on: Y0 (orthonormal) → Y_d, then its
+// CholQR factor; *np_out: the products it ran (iterations it … it + np − 1)
+int cheb_segment(const EigState& s, Chain32& ch, int it, int next_rr, int* np_out) {
+  const ocm_eig::Layout& w = s.w;
+  const int p = s.p, cv_rb = s.pl.cv_rb;
+  const size_t pb = s.pl.pb;
+  hipStream_t st = s.st;
+  const double* Y0 = ch.Wc;
+  if (ch.Mc) {  // Y0 = Wc·Mc
+    hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, ch.Wc, p, ch.Mc, w.T1);
+    OCM_CHECK_LAUNCH("k_cq_apply32 cheb");
+    Y0 = w.T1;
+  }
+  const double a1 = 2.0 / ch.cheb_beta, a2 = 4.0 / ch.cheb_beta;
+  // products in this segment, degree d
+  const int np = std::max(1, std::min(ch.cheb_dmax - (ch.y1_from_w ? 1 : 0), next_rr - it));
+  const int d = np + (ch.y1_from_w ? 1 : 0);
+  double* const buf[4] = {w.T2, w.T1, w.Wa, w.Wb};  // by ocm_eig::SegBuf, which picks each step's output
+  int i1 = ocm_eig::SEG_V, i2 = ocm_eig::SEG_NONE;  // (Y0 is live only as Y_{j−1} or Y_{j−2})
+  for (int c = 0; c < 4; ++c)
+    if (buf[c] == Y0) i1 = c;
+  const double *ym1 = Y0, *ym2 = nullptr;  // Y_{j−1}, Y_{j−2}
+  for (int j = 1; j <= d; ++j) {
+    const int io = ocm_eig::cheb_out(j, d, i1, i2);
+    if (io == ocm_eig::SEG_NONE) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: no free block for the Chebyshev filter");
+    double* out = buf[io];
+    if (j == 1 && ch.y1_from_w) {  // Y1 = X·V = (2/β)·W − V, W = C·V from the test's step
+      hipLaunchKernelGGL(k_axpby, dim3((unsigned)((pb + 255) / 256)), dim3(256), 0, st, w.W, Y0, (int64_t)pb, a1, -1.0,
+                         out);
+      OCM_CHECK_LAUNCH("k_axpby cheb");
+    } else if (j == 1) {  // Y1 = (2/β)·C·Y0 − Y0
+      hipLaunchKernelGGL(k_cv32x, dim3(2 * cv_rb), dim3(512), 0, st, s.C, p, Y0, out, w.cv_part, w.cv_ticket, a1, -1.0,
+                         nullptr, 0.0);
+      OCM_CHECK_LAUNCH("k_cv32x cheb");
+    } else {  // Y_j = (4/β)·C·Y_{j−1} − 2·Y_{j−1} − Y_{j−2}
+      hipLaunchKernelGGL(k_cv32x, dim3(2 * cv_rb), dim3(512), 0, st, s.C, p, ym1, out, w.cv_part, w.cv_ticket, a2, -2.0,
+                         ym2, -1.0);
+      OCM_CHECK_LAUNCH("k_cv32x cheb");
+    }
+    ym2 = ym1;
+    ym1 = out;
+    i2 = i1;
+    i1 = io;
+  }
+  ch.y1_from_w = false;
+  double* Yd = buf[i1];
+  double* Mn = w.Mf + 1024 * ch.mslot;
+  hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, Yd, p, nullptr, nullptr, w.cq_part, w.cq_ticket,
+                     1, (uint64_t)(1500 + it), Mn);
+  OCM_CHECK_LAUNCH("k_cq_gram32 cheb");
+  ch.Wc = Yd;
+  ch.Wn = (Yd == w.Wa) ? w.Wb : w.Wa;
+  ch.Mc = Mn;
+  ch.mslot ^= 1;
+  ch.Sprev = nullptr;
+  *np_out = np;
+  return OCM_OK;
+}
+
+// one plain iteration: W ← (C·Wc)·Mc and its factor, one launch
+int chain_step(const EigState& s, Chain32& ch, int it, int next_rr) {
+  const ocm_eig::Layout& w = s.w;
+  const int cv_rb = s.pl.cv_rb;
+  double* Mn = w.Mf + 1024 * ch.mslot;
+  // the next launch is a plain iteration too: it factors this one's Gram
+  // in a wave of its own (k_cvq32<true>), off the critical path
+  const int defer_next = it + 1 < next_rr ? 1 : 0;
+  double* Sout = w.Sb + 1056 * ch.sslot;
+  if (ch.Sprev)
+    hipLaunchKernelGGL(k_cvq32<true>, dim3(2 * cv_rb), dim3(512), 0, s.st, s.C, s.p, ch.Wc, ch.Mc, ch.Wn, w.cv_part,
+                       w.cv_ticket, w.gpart, w.gtick, (uint64_t)(500 + it), Mn, ch.Sprev, Sout, defer_next);
+  else
+    hipLaunchKernelGGL(k_cvq32<false>, dim3(2 * cv_rb), dim3(512), 0, s.st, s.C, s.p, ch.Wc, ch.Mc, ch.Wn, w.cv_part,
+                       w.cv_ticket, w.gpart, w.gtick, (uint64_t)(500 + it), Mn, nullptr, Sout, defer_next);
+  OCM_CHECK_LAUNCH("k_cvq32");
+  ch.Sprev = defer_next ? Sout : nullptr;
+  ch.sslot ^= 1;
+  ch.Wc = ch.Wn;
+  ch.Wn = (ch.Wn == w.Wa) ? w.Wb : w.Wa;
+  ch.Mc = Mn;
+  ch.mslot ^= 1;
+  return OCM_OK;
+}
+
+// the Rayleigh–Ritz basis V = CholQR2 of the chain's block: T = Wc·Mc and
+// its factor M2 (k_cq_gram32<true>) while a side stream forms C·Wc; then
+// V = T·M2, W = C·V = (C·Wc)·(Mc·M2) and H = VᵀW in one launch
+int rr_basis32(const EigState& s, Chain32& ch, int it) {
+  const ocm_eig::Layout& w = s.w;
+  ocm_ctx* ctx = s.ctx;
+  hipStream_t st = s.st;
+  int rc = eig_side_init(ctx);
+  if (rc) return rc;
+  hipStream_t sc = ctx->eig_side[1];
+  OCM_HIP(hipEventRecord(ctx->eig_ev[0], st));
+  OCM_HIP(hipStreamWaitEvent(sc, ctx->eig_ev[0], 0));
+  hipLaunchKernelGGL(k_cv32, dim3(2 * s.pl.cv_rb), dim3(512), 0, sc, s.C, s.p, ch.Wc, w.T2, w.cv_part, w.cv_ticket);
+  OCM_CHECK_LAUNCH("k_cv32 CWc");
+  OCM_HIP(hipEventRecord(ctx->eig_ev[4], sc));
+  hipLaunchKernelGGL(k_cq_gram32<true>, dim3(CQ_G), dim3(256), 0, st, ch.Wc, s.p, ch.Mc, w.T1, w.cq_part, w.cq_ticket,
+                     0, (uint64_t)(700 + it), w.cq_M);
+  OCM_CHECK_LAUNCH("k_cq_gram32 rr");
+  OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[4], 0));
+  hipLaunchKernelGGL(k_rr_basis32, dim3(CQ_G), dim3(256), 0, st, w.T1, w.T2, s.p, ch.Mc, w.cq_M, w.V, w.W, w.cq_part,
+                     w.cq_ticket, w.H);
+  OCM_CHECK_LAUNCH("k_rr_basis32");
+  ch.Mc = nullptr;
+  return OCM_OK;
+}
+
+// Rayleigh–Ritz on the unrotated block, V, W = C·V and H = VᵀW given: the
+// projection residual R = W − V·H and S = RᵀR, Jacobi on H; the test reads
+// ‖R z_i‖ (at the Jacobi's end).  With θ wanted, R/S, C·R, G2 = Rᵀ(C·R) and
+// the deflation of the whole block run on side streams beside the Jacobi
+// (they need no Ritz rotation: k_theta_combine adds its terms later).  (The
+// eigenproblem of H on the host — implicit QL, ocm_hostla.h — measured
+// slower: ≈ 50–90 µs of QL plus two round trips against the 135 µs Jacobi,
+// profiles/r05m_eig_timeline.txt.)  Leaves the test's θ and residuals in
+// s.hres and, queued, every output of the call as a converged test wants it.
+int rr_step32(const EigState& s) {
+  const ocm_eig::Layout& w = s.w;
+  ocm_ctx* ctx = s.ctx;
+  hipStream_t st = s.st;
+  const int p = s.p, k = s.k, b = s.pl.b, cv_rb = s.pl.cv_rb, theta_mode = s.theta_mode;
+  // two side streams when θ is wanted: A deflates the block and runs θ3;
+  // B forms R and S (handed to the Jacobi's test in flight), then C·R and
+  // G2.  The Jacobi stays on the launch stream, queued first: it then
+  // starts at once on an idle chip (107 µs; 128–145 µs when it started
+  // behind the deflation's workgroups with the θ3 chain on the launch
+  // stream, r05s4–r05s7)
+  hipStream_t sa = st, sb = st;
+  int rc = eig_side_init(ctx);  // the streams and events (the test's read-back event too)
+  if (rc) return rc;
+  if (theta_mode) {
+    sa = ctx->eig_side[0];
+    sb = ctx->eig_side[1];
+    OCM_HIP(hipEventRecord(ctx->eig_ev[0], st));
+    OCM_HIP(hipStreamWaitEvent(sa, ctx->eig_ev[0], 0));
+    OCM_HIP(hipStreamWaitEvent(sb, ctx->eig_ev[0], 0));
+  }
+  double* R = w.T1;
+  double* CR = w.T2;
+  // S reaches the Jacobi's fused test in flight (ctx->eig_flag)
+  const unsigned epoch = ++ctx->eig_epoch;
+  hipLaunchKernelGGL(k_rr_resid32, dim3(CQ_G), dim3(256), 0, sb, w.V, w.W, p, w.H, R, w.cq_part, w.cq_ticket, w.S,
+                     ctx->eig_flag, epoch);
+  OCM_CHECK_LAUNCH("k_rr_resid32");
+  if (theta_mode) {
+    hipLaunchKernelGGL(k_cv32, dim3(2 * cv_rb), dim3(512), 0, sb, s.C, p, R, CR, w.cv_part, w.cv_ticket);
+    OCM_CHECK_LAUNCH("k_cv32 CR");
+    if (theta_mode >= 2) {
+      hipLaunchKernelGGL(k_atb32, dim3(CQ_G), dim3(256), 0, sb, R, CR, p, w.cq_part, w.cq_ticket, w.L);  // G2
+      OCM_CHECK_LAUNCH("k_atb32 G2");
+    }
+    OCM_HIP(hipEventRecord(ctx->eig_ev[3], sb));
+    // after B's test inputs: theta_deflated queues its Δ terms on B too
+    rc = theta_deflated(s, w.V, w.W, w.H, b, sa, sb, ctx->eig_sub, w.tr3);
+    if (rc) return rc;
+    OCM_HIP(hipEventRecord(ctx->eig_ev[2], sa));
+  }
+  // the Jacobi and the test in one launch (the former k_rr_test32's sums)
+  double *theta = w.theta, *res = w.theta + b;
+  rc = jacobi(w.H, b, 40, theta, w.Z, st, w.S, ctx->eig_flag, epoch, k, res);
+  if (rc) return rc;
+  OCM_HIP(hipMemcpyAsync(s.hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
+  OCM_HIP(hipEventRecord(ctx->eig_ev[6], st));
+  // R (= T1) and CR are reused below: side stream B is done with them
+  if (theta_mode) OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[3], 0));
+  // the outputs of a converged test are queued before the host has read
+  // it (the GPU would idle through the round trip otherwise): the Ritz
+  // vectors V·Z into T1, λ and the eigenvectors, then θ once side stream
+  // A is done.  A test that fails leaves them to be overwritten.
+  hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, w.V, p, w.Z, w.T1);  // Ritz vectors
+  OCM_CHECK_LAUNCH("k_cq_apply32 ritz");
+  hipLaunchKernelGGL(k_extract_signfix, dim3(k), dim3(256), 0, st, w.T1, p, b, k, s.evecs_out, theta, s.evals_out,
+                     s.rcond, s.inv_out);
+  OCM_CHECK_LAUNCH("k_extract_signfix");
+  if (theta_mode) {  // (the deflation operands and the θ3 arena are reused by the next test too)
+    OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[2], 0));
+    hipLaunchKernelGGL(k_theta_combine, dim3(1), dim3(256), 0, st, theta, w.Z, w.S, w.L, w.tr3, b, k,
+                       s.slice == 0 ? 1 : 0, theta_mode >= 2 ? 1 : 0, s.theta_out);
+    OCM_CHECK_LAUNCH("k_theta_combine");
+  }
+  OCM_HIP(hipEventSynchronize(ctx->eig_ev[6]));
+  if (ocm_eig::verdict(s.hres, k, b, s.tol).waited_out) {
+    // the fused test gave up waiting for S (side stream B not scheduled
+    // within ≈ 1 s): the launch stream has since waited for B's event, so
+    // the same Jacobi + test runs again with S complete (the same Z and λ;
+    // the outputs queued above read them before this rewrites them)
+    ++ctx->eig_test_reruns;
+    rc = jacobi(w.H, b, 40, theta, w.Z, st, w.S, ctx->eig_flag, epoch, k, res, OCM_JACOBI_SPINS_1S);
+    if (rc) return rc;
+    OCM_HIP(hipMemcpyAsync(s.hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
+    OCM_HIP(hipStreamSynchronize(st));
+    if (ocm_eig::verdict(s.hres, k, b, s.tol).waited_out)
+      return ocm::fail(OCM_ERR_HIP, "ocm_eig_topk: the Rayleigh-Ritz test's operand S was not ready after its "
+                                    "producer finished");
+  }
+  return OCM_OK;
+}
+
+int eig_fused32(const EigState& s, int32_t* iters_out) {
+  const ocm_eig::Layout& w = s.w;
+  hipStream_t st = s.st;
+  const int p = s.p, k = s.k, b = s.pl.b, max_iter = s.max_iter;
+  int next_rr = std::min(PLAIN + 1, max_iter);
+  int rc = eig_start_block(s, next_rr == 1);
+  if (rc) return rc;
+  if (next_rr == 1) {
+    // V = CholQR2 of T1: the Gram and its factor M1, then T = T1·M1 (in place:
+    // every wave rewrites only rows it has read) with the Gram of T and its
+    // factor M2, then V = T·M2
+    hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, w.T1, p, nullptr, nullptr, w.cq_part,
+                       w.cq_ticket, 1, (uint64_t)1, w.cq_M);
+    OCM_CHECK_LAUNCH("k_cq_gram32");
+    hipLaunchKernelGGL(k_cq_gram32<true>, dim3(CQ_G), dim3(256), 0, st, w.T1, p, w.cq_M, w.T1, w.cq_part, w.cq_ticket,
+                       0, (uint64_t)1, w.cq_M + 1024);
+    OCM_CHECK_LAUNCH("k_cq_gram32 apply");
+    hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, w.T1, p, w.cq_M + 1024, w.V);
+    OCM_CHECK_LAUNCH("k_cq_apply32");
+  }
+  Chain32 ch{w.V, w.Wa};
+  ocm_eig::Schedule sched;
+  bool converged = false;
+  int it;
+  for (it = 1; it <= max_iter; ++it) {
+    if (ch.cheb && it < next_rr) {
+      int np = 0;
+      rc = cheb_segment(s, ch, it, next_rr, &np);
+      if (rc) return rc;
+      it += np - 1;  // (the loop adds the last)
+      continue;
+    }
+    if (it < next_rr) {
+      rc = chain_step(s, ch, it, next_rr);
+      if (rc) return rc;
+      continue;
+    }
+    if (ch.Mc) {
+      rc = rr_basis32(s, ch, it);
+      if (rc) return rc;
+    } else {  // the test on the first product (max_iter = 1), V orthonormal: W = C V, H = VᵀW
+      hipLaunchKernelGGL(k_cv32, dim3(2 * s.pl.cv_rb), dim3(512), 0, st, s.C, p, w.V, w.W, w.cv_part, w.cv_ticket);
+      OCM_CHECK_LAUNCH("k_cv32");
+      hipLaunchKernelGGL(k_atb32, dim3(CQ_G), dim3(256), 0, st, w.V, w.W, p, w.cq_part, w.cq_ticket, w.H);
+      OCM_CHECK_LAUNCH("k_atb32 H");
+    }
+    rc = rr_step32(s);
+    if (rc) return rc;
+    const double* h = s.hres;
+    const ocm_eig::Verdict v = ocm_eig::verdict(h, k, b, s.tol);
+    if (v.nan) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: NaN in covariance");
+    converged = v.converged;
+    if (converged || it == max_iter) break;  // evals, evecs and θ are queued
+    const double tb = std::fabs(h[b - 1]);
+    const ocm_eig::Step nx = sched.next(it, max_iter, v.rmax, v.target, std::fabs(h[0]), std::fabs(h[k - 1]), tb, true);
+    next_rr = nx.next_rr;
+    ch.Sprev = nullptr;
+    ch.cheb = nx.use_cheb && next_rr > it + 1;
+    if (ch.cheb) {
+      // the filter starts at the orthonormal basis V, whose C·V = W is in hand
+      ch.cheb_beta = tb;
+      ch.cheb_dmax = nx.dmax;
+      ch.y1_from_w = true;
+      ch.Wc = w.V;
+      ch.Mc = nullptr;
+      continue;
+    }
+    // the chain continues from W = C·V (span is all it needs) and its factor
+    OCM_HIP(hipMemcpyAsync(w.Wa, w.W, s.pl.pb * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, w.Wa, p, nullptr, nullptr, w.cq_part,
+                       w.cq_ticket, 1, (uint64_t)(1000 + it), w.Mf);
+    OCM_CHECK_LAUNCH("k_cq_gram32 chain");
+    ch.Wc = w.Wa;
+    ch.Wn = w.Wb;
+    ch.Mc = w.Mf;
+    ch.mslot = 1;
+  }
+  if (iters_out) *iters_out = std::min(it, max_iter);
+  return converged ? OCM_OK : ocm::fail(OCM_ERR_NOCONV, "ocm_eig_topk: max_iter reached before tolerance");
+}
+
+// ---- b = 48 / 64 on the device, wider blocks with host b×b steps -------------
+// wide: S = AᵀB on the device → host (s.hmat())
+int proj_to_host(const EigState& s, const double* A, const double* B) {
+  int rc = dgemm_ta(A, B, s.p, s.pl.b, s.w.S, s.w.planes, s.pl.plane_cap, s.st);
+  if (rc) return rc;
+  OCM_HIP(hipMemcpyAsync(s.hmat(), s.w.S, s.pl.bb * sizeof(double), hipMemcpyDeviceToHost, s.st));
+  OCM_HIP(hipStreamSynchronize(s.st));
+  return OCM_OK;
+}
+
+// CholQR2 of the column-normalised Win; result in Vout (Win is clobbered)
+int orth_block(const EigState& s, double* Win, double* Vout, uint64_t seed) {
+  const ocm_eig::Layout& w = s.w;
+  hipStream_t st = s.st;
+  const int p = s.p, b = s.pl.b;
+  const size_t pb = s.pl.pb, bb = s.pl.bb;
+  hipLaunchKernelGGL(k_colnormalize, dim3(b), dim3(256), 0, st, Win, p, b, seed);
+  OCM_CHECK_LAUNCH("k_colnormalize");
+  for (int pass = 0; pass < 2; ++pass) {
+    if (s.pl.wide()) {  // pass 0: Win → Vout; pass 1: Vout → Win → Vout (the GEMM cannot run in place)
+      double* src = pass == 0 ? Win : Vout;
+      double* dst = pass == 0 ? Vout : Win;
+      double* hmat = s.hmat();
+      int rc = proj_to_host(s, src, src);
+      if (rc) return rc;
+      ocm::host_chol_inv_t(hmat, b, hmat + bb);
+      OCM_HIP(hipMemcpyAsync(w.L, hmat + bb, bb * sizeof(double), hipMemcpyHostToDevice, st));
+      rc = dgemm(src, b, w.L, b, dst, b, p, b, b, 1, nullptr, st);
+      if (rc) return rc;
+      if (pass == 1) OCM_HIP(hipMemcpyAsync(Vout, Win, pb * sizeof(double), hipMemcpyDeviceToDevice, st));
+      OCM_HIP(hipStreamSynchronize(st));  // hmat is reused by the next pass
+      continue;
+    }
+    double* src = pass == 0 ? Win : Vout;  // b = 48 or 64
+    int rc = atb(src, src, p, b, w.S, w.apart, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_chol, dim3(1), dim3(256), 0, st, w.S, b, w.L);
+    OCM_CHECK_LAUNCH("k_chol");
+    rc = trsm_rows(src, w.L, p, b, Vout, st);
+    if (rc) return rc;
+  }
+  return OCM_OK;
+}
+
+// out = Aᵀ B (b×b) on the device
+int project(const EigState& s, const double* A, const double* B, double* out) {
+  if (s.pl.wide()) return dgemm_ta(A, B, s.p, s.pl.b, out, s.w.planes, s.pl.plane_cap, s.st);
+  return atb(A, B, s.p, s.pl.b, out, s.w.apart, s.st);
+}
+
+// Ritz values (theta, descending) and rotations Z of H = Vᵀ W
+int ritz(const EigState& s, const double* V, const double* W) {
+  const ocm_eig::Layout& w = s.w;
+  const int b = s.pl.b;
+  const size_t bb = s.pl.bb;
+  if (!s.pl.wide()) {
+    int rc = project(s, V, W, w.H);
+    if (rc) return rc;
+    return jacobi(w.H, b, 40, w.theta, w.Z, s.st);
+  }
+  int rc = proj_to_host(s, V, W);
+  if (rc) return rc;
+  double* hmat = s.hmat();
+  if (!ocm::host_sym_eig(hmat, b, hmat + 2 * bb, hmat + bb)) {
+    ocm::set_error("ocm_eig_topk: implicit QL of the Rayleigh-Ritz problem did not converge");
+    return OCM_ERR_NOCONV;
+  }
+  OCM_HIP(hipMemcpyAsync(w.Z, hmat + bb, bb * sizeof(double), hipMemcpyHostToDevice, s.st));
+  OCM_HIP(hipMemcpyAsync(w.theta, hmat + 2 * bb, b * sizeof(double), hipMemcpyHostToDevice, s.st));
+  return OCM_OK;
+}
+
+int eig_block(const EigState& s, int32_t* iters_out) {
+  const ocm_eig::Layout& w = s.w;
+  hipStream_t st = s.st;
+  const int p = s.p, k = s.k, b = s.pl.b, max_iter = s.max_iter;
+  const size_t pb = s.pl.pb;
+  double *V = w.V, *W = w.W, *T1 = w.T1, *T2 = w.T2, *theta = w.theta, *res = w.theta + b;
+  int next_rr = std::min(PLAIN + 1, max_iter);
+  int rc = eig_start_block(s, next_rr == 1);
+  if (rc) return rc;
+  if (next_rr == 1) {
+    rc = orth_block(s, T1, V, 1);
+    if (rc) return rc;
+  }
+  ocm_eig::Schedule sched;
+  bool converged = false;
+  int it;
+  for (it = 1; it <= max_iter; ++it) {
+    rc = dgemm(s.C, p, V, b, W, b, p, b, p, s.pl.ksplit, w.planes, st);  // W = C V
+    if (rc) return rc;
+    if (it < next_rr) {  // W is not needed again (recomputed next iteration)
+      rc = orth_block(s, W, V, 500 + it);
+      if (rc) return rc;
+      continue;
+    }
+    rc = ritz(s, V, W);
+    if (rc) return rc;
+    rc = dgemm(V, b, w.Z, b, T1, b, p, b, b, 1, nullptr, st);  // Ritz vectors
+    if (rc) return rc;
+    rc = dgemm(W, b, w.Z, b, T2, b, p, b, b, 1, nullptr, st);  // C · Ritz vectors
+    if (rc) return rc;
+    std::swap(V, T1);
+    std::swap(W, T2);
+    hipLaunchKernelGGL(k_ritz_residual, dim3(k), dim3(256), 0, st, W, V, theta, p, b, res);
+    OCM_CHECK_LAUNCH("k_ritz_residual");
+    OCM_HIP(hipMemcpyAsync(s.hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
+    OCM_HIP(hipStreamSynchronize(st));
+    const double* h = s.hres;
+    const ocm_eig::Verdict v = ocm_eig::verdict(h, k, b, s.tol);
+    if (v.nan) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: NaN in covariance");
+    converged = v.converged;
+    if (converged || it == max_iter) break;  // V, W, theta are consistent for the outputs
+    next_rr = sched.next(it, max_iter, v.rmax, v.target, std::fabs(h[0]), std::fabs(h[k - 1]), std::fabs(h[b - 1]),
+                         false).next_rr;
+    // next basis: orth(C · Ritz vectors)
+    OCM_HIP(hipMemcpyAsync(T1, W, pb * sizeof(double), hipMemcpyDeviceToDevice, st));
+    rc = orth_block(s, T1, V, 1000 + it);
+    if (rc) return rc;
+  }
+  if (iters_out) *iters_out = std::min(it, max_iter);
+  hipLaunchKernelGGL(k_extract_signfix, dim3(k), dim3(256), 0, st, V, p, b, k, s.evecs_out, theta, s.evals_out);
+  OCM_CHECK_LAUNCH("k_extract_signfix");
+  if (s.inv_out) hipLaunchKernelGGL(k_inv_evals, dim3(1), dim3(256), 0, st, s.evals_out, k, s.rcond, s.inv_out);
+  if (s.theta_mode) {
+    // H_k = V_kᵀ (C V_k): the projected block of the Ritz vectors; deflate
+    // the leading k of them
+    rc = project(s, V, W, w.H);
+    if (rc) return rc;
+    rc = theta_deflated(s, V, W, w.H, k, st, st, s.ctx, s.theta_out);
+    if (rc) return rc;
+  }
+  return converged ? OCM_OK : ocm::fail(OCM_ERR_NOCONV, "ocm_eig_topk: max_iter reached before tolerance");
+}
+
 int eig_topk_impl(ocm_ctx* ctx, const double* C, int32_t p, int32_t k, double tol, int32_t max_iter,
                   int32_t theta_mode, int32_t slice, int32_t nslices, double* evals_out, double* evecs_out,
                   double* theta_out, int32_t* iters_out, hipStream_t st, double* inv_out = nullptr,
                   double rcond = 1e-15) {
   if (tol <= 0) tol = 1e-10;
   if (max_iter <= 0) max_iter = 2000;
-
-  if (p <= JMAX) {
-    void* w = ocm::workspace(ctx, (size_t)(p + p * p + 64) * sizeof(double), st);
-    if (!w) return OCM_ERR_NOMEM;
-    ocm::Carve cv{static_cast<char*>(w)};
-    double* ev = cv.take<double>(p);
-    double* Z = cv.take<double>((size_t)p * p);
-    int rc = jacobi(C, p, 60, ev, Z, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(64), 0, st, ev, Z, p, k, evals_out, evecs_out,
-                       theta_mode ? theta_out : nullptr);
-    OCM_CHECK_LAUNCH("k_small_finish");
-    if (inv_out) hipLaunchKernelGGL(k_inv_evals, dim3(1), dim3(256), 0, st, evals_out, k, rcond, inv_out);
-    if (theta_mode && slice != 0) OCM_HIP(hipMemsetAsync(theta_out + 2, 0, sizeof(double), st));
-    if (iters_out) *iters_out = 1;
-    return OCM_OK;
+  EigState s{ctx, st, C, p, k, tol, max_iter, theta_mode, slice, nslices, evals_out, evecs_out, theta_out, inv_out,
+             rcond};
+  s.pl = ocm_eig::make_plan(p, k, theta_mode);
+  OCM_REQUIRE(s.pl.ok, "ocm_eig_topk: p too small for the block path");
+  ocm::Carve measure{nullptr};
+  ocm_eig::carve(s.pl, measure);
+  void* ws = ocm::workspace(ctx, measure.off, st);
+  if (!ws) return OCM_ERR_NOMEM;
+  ocm::Carve cv{static_cast<char*>(ws)};
+  s.w = ocm_eig::carve(s.pl, cv);
+  if (s.pl.path == ocm_eig::Path::small) {
+    const int rc = eig_small(s);
+    if (!rc && iters_out) *iters_out = 1;
+    return rc;
   }
-
-  // block size: k plus oversampling, a multiple of 16, ≤ p
-  int b = ((k + std::max(8, k / 2)) + 15) / 16 * 16;
-  b = std::max(b, 32);
-  if (k <= JMAX && b > JMAX) b = JMAX;
-  if (b > p) b = std::max(k, (p / 16) * 16);
-  OCM_REQUIRE(b >= k && b >= 16, "ocm_eig_topk: p too small for the block path");
-  const bool wide = b > JMAX;  // host b×b steps
-
-  const int ksplit = std::max(1, std::min(16, (int)(256 / std::max(1, ((p + 63) / 64) * ((b + 63) / 64)))));
-  const size_t pb = (size_t)p * b, bb = (size_t)b * b;
-  const int nblk = (p + 63) / 64;
-  const size_t def_blocks = (size_t)((p + DT - 1) / DT) * ((p + DT - 1) / DT);  // deflate GEMM tiles
-  const size_t plane_cap = std::max((size_t)ksplit * pb, wide ? 16 * bb : 0);
-  size_t need = (5 * pb + 6 * bb + plane_cap + (wide ? 0 : (size_t)nblk * bb) + 4 * b + 64) * sizeof(double);
-  need += ((size_t)CQ_G * 1024 + 2048 + 64) * sizeof(double) + 3 * 256;  // CholQR / k_atb32 partials, M1/M2, ticket
-  const int cv_rb = (p + 15) / 16;  // k_cv32 row blocks
-  need += ((size_t)cv_rb * 2 * 512) * sizeof(double) + (size_t)cv_rb * sizeof(unsigned) + 2 * 256;
-  // fused plain iterations (k_cvq32, b = 32): two blocks, two factors, the
-  // Gram partials (row blocks + groups) and the two-level counters
-  const bool fused = !wide && b == QB;
-  const int cvq_ng = (cv_rb + CVQ_G1 - 1) / CVQ_G1;
-  const int gt_words = (1 + cvq_ng) * TICKET_STRIDE;
-  if (fused) need += (2 * pb + 2048 + (size_t)(cv_rb + cvq_ng) * 1024 + 2 * 1056) * sizeof(double) + gt_words * 4 + 5 * 256;
-  if (theta_mode) need += (4 * (size_t)b * p + 2 * def_blocks + 8) * sizeof(double) + 4 * 256;
-  void* w = ocm::workspace(ctx, need + 16 * 256, st);
-  if (!w) return OCM_ERR_NOMEM;
-  ocm::Carve cv{static_cast<char*>(w)};
-  double* V = cv.take<double>(pb);
-  double* W = cv.take<double>(pb);
-  double* T1 = cv.take<double>(pb);
-  double* T2 = cv.take<double>(pb);
-  double* H = cv.take<double>(bb);
-  double* Z = cv.take<double>(bb);
-  double* S = cv.take<double>(bb);
-  double* L = cv.take<double>(bb);
-  double* theta = cv.take<double>(2 * (size_t)b);  // θ (b), then the residuals (b): one read-back
-  double* res = theta + b;
-  double* planes = cv.take<double>(plane_cap);
-  double* apart = wide ? nullptr : cv.take<double>((size_t)nblk * bb);
-  double* cq_part = cv.take<double>((size_t)CQ_G * 1024);
-  double* cq_M = cv.take<double>(2048);
-  // k_cq_gram32's ticket counts from a multiple of CQ_G, k_cv32's parity tickets
-  // start even: both zeroed by the k_randn launch below (contiguous)
-  unsigned* cq_ticket = cv.take<unsigned>(64);
-  double* cv_part = cv.take<double>((size_t)cv_rb * 2 * 512);
-  // k_cv32's parity tickets, then k_cvq32's counters: one range, zeroed once
-  unsigned* cv_ticket = cv.take<unsigned>(cv_rb + (fused ? gt_words + TICKET_STRIDE : 0));
-  unsigned* gtick = fused ? cv_ticket + (cv_rb + TICKET_STRIDE - 1) / TICKET_STRIDE * TICKET_STRIDE : nullptr;
-  const int nzero_cv = fused ? (int)(gtick - cv_ticket) + gt_words : cv_rb;
-  double* Wa = fused ? cv.take<double>(pb) : nullptr;
-  double* Wb = fused ? cv.take<double>(pb) : nullptr;
-  double* Mf = fused ? cv.take<double>(2048) : nullptr;
-  double* gpart = fused ? cv.take<double>((size_t)(cv_rb + cvq_ng) * 1024) : nullptr;
-  double* Sb = fused ? cv.take<double>(2 * 1056) : nullptr;  // two deferred Grams (+ their flags)
-  // θ work buffers (the deflated matrix, its tile partials, the rank-2kd
-  // operands, three traces), carved up front: the fused path fills them during
-  // its Rayleigh–Ritz step, on a side stream
-  double* dpart = theta_mode ? cv.take<double>(2 * def_blocks) : nullptr;
-  double* Ud = theta_mode ? cv.take<double>((size_t)2 * b * p) : nullptr;
-  double* Wd = theta_mode ? cv.take<double>((size_t)2 * b * p) : nullptr;
-  double* tr3 = theta_mode ? cv.take<double>(8) : nullptr;
-  auto* hres = static_cast<double*>(ocm::host_staging(ctx, (wide ? 3 * bb + b : 2 * b) * sizeof(double)));
-  if (!hres) return OCM_ERR_NOMEM;
-  double* hmat = hres + 2 * b;  // wide: b×b host staging (+ b×b result, + b values)
-
-  // wide: S = AᵀB on the device → host
-  auto proj_to_host = [&](const double* A, const double* B) -> int {
-    int rc = dgemm_ta(A, B, p, b, S, planes, plane_cap, st);
-    if (rc) return rc;
-    OCM_HIP(hipMemcpyAsync(hmat, S, bb * sizeof(double), hipMemcpyDeviceToHost, st));
-    OCM_HIP(hipStreamSynchronize(st));
-    return OCM_OK;
-  };
-
-  using ocm::host_chol_inv_t;
-  using ocm::host_sym_eig;
-  auto orth = [&](double* Win, double* Vout, uint64_t seed, int passes) -> int {
-    // CholQR (passes = 1) or CholQR2 on column-normalised Win; result in Vout
-    // (Win is clobbered).  b = 32: k_cq_gram32 (the Gram and its factor, one per pass)
-    // and one k_cq_apply32, each over CQ_G workgroups; b = 48 / 64: the `passes`
-    // argument is not read, both passes always run.
-    if (!wide && b == QB) {
-      hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, Win, p, nullptr, nullptr, cq_part,
-                         cq_ticket, 1, seed, cq_M);
-      OCM_CHECK_LAUNCH("k_cq_gram32");
-      const double* src = Win;
-      if (passes == 2) {  // T = Win·M1 (in place: every wave rewrites only rows it has read) + Gram of T
-        hipLaunchKernelGGL(k_cq_gram32<true>, dim3(CQ_G), dim3(256), 0, st, Win, p, cq_M, Win, cq_part, cq_ticket, 0,
-                           seed, cq_M + 1024);
-        OCM_CHECK_LAUNCH("k_cq_gram32 apply");
-        hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, src, p, cq_M + 1024, Vout);
-      } else {
-        hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, src, p, cq_M, Vout);
-      }
-      OCM_CHECK_LAUNCH("k_cq_apply32");
-      return OCM_OK;
-    }
-    hipLaunchKernelGGL(k_colnormalize, dim3(b), dim3(256), 0, st, Win, p, b, seed);
-    OCM_CHECK_LAUNCH("k_colnormalize");
-    for (int pass = 0; pass < 2; ++pass) {
-      if (wide) {  // pass 0: Win → Vout; pass 1: Vout → Win → Vout (the GEMM cannot run in place)
-        double* src = pass == 0 ? Win : Vout;
-        double* dst = pass == 0 ? Vout : Win;
-        int rc = proj_to_host(src, src);
-        if (rc) return rc;
-        host_chol_inv_t(hmat, b, hmat + bb);
-        OCM_HIP(hipMemcpyAsync(L, hmat + bb, bb * sizeof(double), hipMemcpyHostToDevice, st));
-        rc = dgemm(src, b, L, b, dst, b, p, b, b, 1, nullptr, st);
-        if (rc) return rc;
-        if (pass == 1) OCM_HIP(hipMemcpyAsync(Vout, Win, pb * sizeof(double), hipMemcpyDeviceToDevice, st));
-        OCM_HIP(hipStreamSynchronize(st));  // hmat is reused by the next pass
-        continue;
-      }
-      double* src = pass == 0 ? Win : Vout;  // b = 48 or 64 (b = 32 returned above)
-      int rc = atb(src, src, p, b, S, apart, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_chol, dim3(1), dim3(256), 0, st, S, b, L);
-      OCM_CHECK_LAUNCH("k_chol");
-      rc = trsm_rows(src, L, p, b, Vout, st);
-      if (rc) return rc;
-    }
-    return OCM_OK;
-  };
-  // H = Vᵀ W (b×b) on the device
-  auto project = [&](const double* A, const double* B, double* out) -> int {
-    if (wide) return dgemm_ta(A, B, p, b, out, planes, plane_cap, st);
-    return atb(A, B, p, b, out, apart, st);
-  };
-  // Ritz values (theta, descending) and rotations Z of H = Vᵀ W
-  auto ritz = [&]() -> int {
-    if (!wide) {
-      int rc = project(V, W, H);
-      if (rc) return rc;
-      return jacobi(H, b, 40, theta, Z, st);
-    }
-    int rc = proj_to_host(V, W);
-    if (rc) return rc;
-    if (!host_sym_eig(hmat, b, hmat + 2 * bb, hmat + bb)) {
-      ocm::set_error("ocm_eig_topk: implicit QL of the Rayleigh-Ritz problem did not converge");
-      return OCM_ERR_NOCONV;
-    }
-    OCM_HIP(hipMemcpyAsync(Z, hmat + bb, bb * sizeof(double), hipMemcpyHostToDevice, st));
-    OCM_HIP(hipMemcpyAsync(theta, hmat + 2 * bb, b * sizeof(double), hipMemcpyHostToDevice, st));
-    return OCM_OK;
-  };
-
-  // θ1..θ3 of (I − P)C(I − P), P the projector on the first kd columns of the
-  // orthonormal block Vb (Wb_ = C·Vb, Hb = Vbᵀ Wb_): the rank-2kd deflation
-  // GEMM with its trace and Frobenius epilogue → out3[0..1], and this slice's
-  // θ3 rows → out3[2], all on stream s; the θ3 Gram runs on gctx's workspaces.
-  auto theta_into = [&](const double* Vb, const double* Wb_, const double* Hb, int kd, hipStream_t s,
-                        hipStream_t s2, ocm_ctx* gctx, double* out3) -> int {
-    // s2 (≠ s: the fused path's second side stream) takes the Δ terms beside
-    // the θ3 Gram; eig_ev[4] / [5] order them
-    hipLaunchKernelGGL(k_deflate_operands_h, dim3((unsigned)(((size_t)p * kd + 255) / 256)), dim3(256), 0, s, Vb,
-                       Wb_, Hb, p, b, kd, Ud, Wd);
-    OCM_CHECK_LAUNCH("k_deflate_operands_h");
-    // the deflated matrix D = C − U·Wdᵀ is never stored in fp64: k_dgemm<3>
-    // writes its off-diagonal part O (float32, the θ3 Gram's input), its
-    // diagonal Δ, per-tile row sums of O² and the {tr D, ‖D‖²} partials.  O
-    // and the partials live in gctx's second arena (the Gram takes gctx's
-    // workspace).
-    const size_t pp = (size_t)p * p;
-    const int ntc = (p + DT - 1) / DT;
-    const int ntq = (p + 127) / 128;
-    const int ntr_cap = ntq * (ntq + 1) / 2 * 16;  // k_gram_trace partials
-    const size_t o32_bytes = (pp * sizeof(float) + 255) / 256 * 256;
-    char* aux = static_cast<char*>(ocm::workspace_aux(
-        gctx, o32_bytes + (2 * (size_t)p + (size_t)ntc * p + ntr_cap + 64) * sizeof(double), s));
-    if (!aux) return OCM_ERR_NOMEM;
-    float* O32 = reinterpret_cast<float*>(aux);
-    double* diag = reinterpret_cast<double*>(aux + o32_bytes);
-    double* rowpart = diag + p;
-    double* dpart3 = rowpart + (size_t)ntc * p;  // ≤ p/256 + 1 workgroup partials
-    double* trpart = dpart3 + p;
-    const dim3 gd(ntc, ntc, 1);
-    if (2 * kd <= 64)
-      hipLaunchKernelGGL(k_deflate64, gd, dim3(256), 0, s, Ud, (int64_t)(2 * kd), Wd, (int64_t)p, diag, p, p, 2 * kd, C,
-                         (int64_t)p, dpart, O32, rowpart);
-    else
-      hipLaunchKernelGGL(k_dgemm<3>, gd, dim3(256), 0, s, Ud, (int64_t)(2 * kd), Wd, (int64_t)p, diag, (int64_t)p, p,
-                         p, 2 * kd, 2 * kd, C, (int64_t)p, dpart, 0, O32, rowpart);
-    OCM_CHECK_LAUNCH("k_dgemm deflate");
-    // the tile pairs sit in this context's workspace, which the θ3 Gram takes
-    // over when gctx is this context (the unfused path): sum them first there
-    const bool own_ws = gctx == ctx;
-    if (own_ws) {
-      hipLaunchKernelGGL(k_theta_final, dim3(1), dim3(256), 0, s, dpart, (int)(gd.x * gd.y), nullptr, 0, nullptr, 0,
-                         out3, 1);
-      OCM_CHECK_LAUNCH("k_theta_final pairs");
-    }
-    // θ3 = Σ Δ³ + 3 Σ Δ_i Σ_j O_ij² + Σ O∘(O²): this slice's rows of the Δ
-    // terms (on s2), and the i8×3 Gram of its rows of O paired with all of O
-    // in the Gram's epilogue (k_gram_trace, on s)
-    const int r0 = (int)((int64_t)p * slice / nslices), r1 = (int)((int64_t)p * (slice + 1) / nslices);
-    int nb3 = 0, ntr = 0;
-    if (theta_mode >= 2 && r1 > r0) {
-      const int nr = r1 - r0;
-      nb3 = (nr + 255) / 256;
-      if (s2 != s) {
-        OCM_HIP(hipEventRecord(ctx->eig_ev[4], s));
-        OCM_HIP(hipStreamWaitEvent(s2, ctx->eig_ev[4], 0));
-      }
-      hipLaunchKernelGGL(k_theta3_rows, dim3(nb3), dim3(256), 0, s2, diag, rowpart, ntc, p, r0, r1, dpart3);
-      OCM_CHECK_LAUNCH("k_theta3_rows");
-      if (s2 != s) OCM_HIP(hipEventRecord(ctx->eig_ev[5], s2));
-      int rc2 = ocm::trace_gram_rows_i8(gctx, O32 + (size_t)r0 * p, p, nr, p, O32, trpart, &ntr, s);
-      if (rc2) return rc2;
-      if (s2 != s) OCM_HIP(hipStreamWaitEvent(s, ctx->eig_ev[5], 0));
-    }
-    hipLaunchKernelGGL(k_theta_final, dim3(1), dim3(256), 0, s, dpart, own_ws ? 0 : (int)(gd.x * gd.y), dpart3, nb3,
-                       trpart, ntr, out3, own_ws ? 2 : 3);
-    OCM_CHECK_LAUNCH("k_theta_final");
-    return OCM_OK;
-  };
-
-  // V₀: a Gaussian block, used as it is — the subspace after i iterations is
-  // span(Cⁱ V₀) whatever basis V₀ has, so only the Rayleigh–Ritz steps need an
-  // orthonormal basis (every iteration before one ends with CholQR2), and an
-  // orthonormalisation of V₀ costs a CholQR pass (≈ 36 µs) for nothing
-  hipLaunchKernelGGL(k_randn, dim3((unsigned)((std::max<size_t>(pb, nzero_cv) + 255) / 256)), dim3(256), 0, st, V,
-                     (int64_t)pb, 0x5EEDull, cq_ticket, 1, cv_ticket, nzero_cv);
-  OCM_CHECK_LAUNCH("k_randn");
-  int rc = OCM_OK;
-
-  // Iterations are plain orthogonal iterations V ← orth(C V) except at the
-  // Rayleigh–Ritz steps, which are the only ones that can test convergence:
-  // the subspace after iteration i is span(Cⁱ V₀) whatever rotations happen in
-  // between, so Rayleigh–Ritz only has to run where the test can pass.  A
-  // Rayleigh–Ritz step costs ~5 plain iterations (a 32×32 Jacobi on the
-  // projection, two rotations, the residuals and a host read of them), so the
-  // next one is scheduled where the residual is predicted to reach the
-  // tolerance: the max residual (that of Ritz pair k) shrinks by λ_{b+1}/λ_k
-  // per iteration, estimated by θ_b/θ_k (θ_b ≤ λ_b) and, from the second test
-  // on, by the measured decay since the last one, whichever is slower.  A
-  // short prediction costs one more test, a long one a few plain iterations
-  // past convergence; the stopping rule itself is unchanged.  The first test
-  // comes at iteration PLAIN + 1: the spectra of the bench data (p = 2048,
-  // k = 20) converge at iteration 5, the derivative spectra of the nuts
-  // preprocessing (simca_nuts.py:47-52) at ~33.
-  constexpr int PLAIN = 4;
-  int it = 0, next_rr = std::min(PLAIN + 1, max_iter), prev_it = 0;
-  if (next_rr == 1) {  // Rayleigh–Ritz on the first product: V₀ must be orthonormal
-    hipLaunchKernelGGL(k_randn, dim3((unsigned)((pb + 255) / 256)), dim3(256), 0, st, T1, (int64_t)pb, 0x5EEDull);
-    OCM_CHECK_LAUNCH("k_randn");
-    rc = orth(T1, V, 1, 2);
-    if (rc) return rc;
-  }
-  double prev_rmax = 0.0;
-  bool converged = false;
-  bool extracted = false;  // the fused path writes evals / evecs itself
-  // fused chain state (b = 32): the current unnormalised block Wc and its
-  // CholQR factor Mc (nullptr: Wc is the start block, used as it is)
-  double* Wc = V;
-  double* Wn = Wa;
-  const double* Mc = nullptr;
-  int mslot = 0;
-  const double* Sprev = nullptr;  // the Gram the previous plain launch left unfactored (k_cvq32<true>)
-  int sslot = 0;
-  // Chebyshev-filtered iterations, from the first failed
-  // Rayleigh–Ritz test on: the test's Ritz values bound the unwanted spectrum
-  // (λ_{b+1} … λ_p ≤ θ_b up to the test's accuracy; C is PSD, so ≥ 0), and a
-  // degree-d Chebyshev polynomial T_d(X), X = 2C/θ_b − I, damps [0, θ_b] to
-  // ≤ 1 while it amplifies λ_k by T_d(2λ_k/θ_b − 1) ≈ e^{d·acosh(2λ_k/θ_b − 1)}
-  // — for a slow gap (λ_k/θ_b = 1 + δ) a rate of e^{−2√δ} per product against
-  // (1 + δ)^{−1} for the plain iteration.  Each product is one three-term step
-  // Y_{j+1} = (4/θ_b)·C·Y_j − 2Y_j − Y_{j−1} (k_cv32x) with no CholQR in
-  // between; a segment ends with one CholQR factor once the block's condition
-  // would pass ≈ 1e6 (T_d(x_1) ≤ 1e6, x_1 = 2θ_1/θ_b − 1), and the next segment
-  // restarts the recurrence from the orthonormalised block.  Before the first
-  // test nothing bounds λ_{b+1} (the bench data converge at that test), so the
-  // plain iterations stay.
-  bool cheb = false;          // filtered continuation active
-  bool cheb_prev = false;     // the interval before the last test was filtered
-  bool y1_from_w = false;     // the segment starts at the Rayleigh–Ritz basis V with C·V = W in hand
-  double cheb_beta = 0.0;
-  int cheb_dmax = 1;
-  auto cheb_degree_cap = [](double x1) {
-    int d = 1;
-    while (d < 8 && std::cosh((d + 1) * std::acosh(x1)) <= 1e6) ++d;
-    return d;
-  };
-  for (it = 1; it <= max_iter; ++it) {
-    if (fused && cheb && it < next_rr) {
-      // one filter segment: Y0 (orthonormal) → Y_d, then its CholQR factor
-      const double* Y0 = Wc;
-      if (Mc) {  // Y0 = Wc·Mc
-        hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, Wc, p, Mc, T1);
-        OCM_CHECK_LAUNCH("k_cq_apply32 cheb");
-        Y0 = T1;
-      }
-      const double a1 = 2.0 / cheb_beta, a2 = 4.0 / cheb_beta;
-      // products in this segment (iterations it .. it + np − 1), degree d
-      const int np = std::max(1, std::min(cheb_dmax - (y1_from_w ? 1 : 0), next_rr - it));
-      const int d = np + (y1_from_w ? 1 : 0);
-      // buffers: intermediates prefer T2, T1, Wa; the last degree lands in a
-      // chain buffer (Wb is never an intermediate, so one is always free)
-      double* pool[4] = {T2, T1, Wa, Wb};
-      const double* ym2 = nullptr;  // Y_{j−2}
-      const double* ym1 = Y0;       // Y_{j−1}
-      for (int j = 1; j <= d; ++j) {
-        double* out = nullptr;
-        if (j == d) {
-          for (double* c2 : {Wa, Wb})
-            if (c2 != ym1 && c2 != ym2) { out = c2; break; }
-        } else {  // (Y0 is live only as Y_{j−1} or Y_{j−2})
-          for (double* c2 : pool)
-            if (c2 != ym1 && c2 != ym2) { out = c2; break; }
-        }
-        if (!out) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: no free block for the Chebyshev filter");
-        if (j == 1 && y1_from_w) {  // Y1 = X·V = (2/β)·W − V, W = C·V from the test's step
-          hipLaunchKernelGGL(k_axpby, dim3((unsigned)((pb + 255) / 256)), dim3(256), 0, st, W, Y0, (int64_t)pb, a1,
-                             -1.0, out);
-          OCM_CHECK_LAUNCH("k_axpby cheb");
-        } else if (j == 1) {  // Y1 = (2/β)·C·Y0 − Y0
-          hipLaunchKernelGGL(k_cv32x, dim3(2 * cv_rb), dim3(512), 0, st, C, p, Y0, out, cv_part, cv_ticket, a1, -1.0,
-                             nullptr, 0.0);
-          OCM_CHECK_LAUNCH("k_cv32x cheb");
-        } else {  // Y_j = (4/β)·C·Y_{j−1} − 2·Y_{j−1} − Y_{j−2}
-          hipLaunchKernelGGL(k_cv32x, dim3(2 * cv_rb), dim3(512), 0, st, C, p, ym1, out, cv_part, cv_ticket, a2, -2.0,
-                             ym2, -1.0);
-          OCM_CHECK_LAUNCH("k_cv32x cheb");
-        }
-        ym2 = ym1;
-        ym1 = out;
-      }
-      y1_from_w = false;
-      double* Yd = const_cast<double*>(ym1);
-      double* Mn = Mf + 1024 * mslot;
-      hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, Yd, p, nullptr, nullptr, cq_part, cq_ticket,
-                         1, (uint64_t)(1500 + it), Mn);
-      OCM_CHECK_LAUNCH("k_cq_gram32 cheb");
-      Wc = Yd;
-      Wn = (Yd == Wa) ? Wb : Wa;
-      Mc = Mn;
-      mslot ^= 1;
-      Sprev = nullptr;
-      it += np - 1;  // (the loop adds the last)
-      continue;
-    }
-    if (fused && it < next_rr) {  // W ← (C·Wc)·Mc and its factor, one launch
-      double* Mn = Mf + 1024 * mslot;
-      // the next launch is a plain iteration too: it factors this one's Gram
-      // in a wave of its own (k_cvq32<true>), off the critical path
-      const int defer_next = it + 1 < next_rr ? 1 : 0;
-      double* Sout = Sb + 1056 * sslot;
-      if (Sprev)
-        hipLaunchKernelGGL(k_cvq32<true>, dim3(2 * cv_rb), dim3(512), 0, st, C, p, Wc, Mc, Wn, cv_part, cv_ticket,
-                           gpart, gtick, (uint64_t)(500 + it), Mn, Sprev, Sout, defer_next);
-      else
-        hipLaunchKernelGGL(k_cvq32<false>, dim3(2 * cv_rb), dim3(512), 0, st, C, p, Wc, Mc, Wn, cv_part, cv_ticket,
-                           gpart, gtick, (uint64_t)(500 + it), Mn, nullptr, Sout, defer_next);
-      OCM_CHECK_LAUNCH("k_cvq32");
-      Sprev = defer_next ? Sout : nullptr;
-      sslot ^= 1;
-#ifdef OCM_CVQ_STAMPS
-      {
-        unsigned long long h[10];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cvq_st), sizeof(h));
-        fprintf(stderr, "cvq32 us: product+factor %.2f (product waves end %.2f, factor wave end %.2f) pair %.2f "
-                "gram %.2f group %.2f last %.2f sum %.2f finalize %.2f\n",
-                (h[1] - h[0]) / 100.0, h[9] ? (h[9] - h[0]) / 100.0 : -1.0, h[8] ? (h[8] - h[0]) / 100.0 : -1.0,
-                (h[2] - h[1]) / 100.0, (h[3] - h[2]) / 100.0, (h[4] - h[3]) / 100.0,
-                (h[5] - h[4]) / 100.0, (h[6] - h[5]) / 100.0, (h[7] - h[6]) / 100.0);
-        unsigned long long z[10] = {~0ull, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_cvq_st), z, sizeof(z));
-      }
-#endif
-      Wc = Wn;
-      Wn = (Wn == Wa) ? Wb : Wa;
-      Mc = Mn;
-      mslot ^= 1;
-      continue;
-    }
-    bool basis_fused = false;
-    if (fused && Mc) {
-      // the Rayleigh–Ritz basis V = CholQR2 of the chain's block: T = Wc·Mc and
-      // its factor M2 (k_cq_gram32<true>) while a side stream forms C·Wc; then
-      // V = T·M2, W = C·V = (C·Wc)·(Mc·M2) and H = VᵀW in one launch
-      rc = eig_side_init(ctx);
-      if (rc) return rc;
-      hipStream_t sc = ctx->eig_side[1];
-      OCM_HIP(hipEventRecord(ctx->eig_ev[0], st));
-      OCM_HIP(hipStreamWaitEvent(sc, ctx->eig_ev[0], 0));
-      hipLaunchKernelGGL(k_cv32, dim3(2 * cv_rb), dim3(512), 0, sc, C, p, Wc, T2, cv_part, cv_ticket);
-      OCM_CHECK_LAUNCH("k_cv32 CWc");
-      OCM_HIP(hipEventRecord(ctx->eig_ev[4], sc));
-      hipLaunchKernelGGL(k_cq_gram32<true>, dim3(CQ_G), dim3(256), 0, st, Wc, p, Mc, T1, cq_part, cq_ticket, 0,
-                         (uint64_t)(700 + it), cq_M);
-      OCM_CHECK_LAUNCH("k_cq_gram32 rr");
-      OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[4], 0));
-      hipLaunchKernelGGL(k_rr_basis32, dim3(CQ_G), dim3(256), 0, st, T1, T2, p, Mc, cq_M, V, W, cq_part, cq_ticket,
-                         H);
-      OCM_CHECK_LAUNCH("k_rr_basis32");
-      Mc = nullptr;
-      basis_fused = true;
-    }
-    if (basis_fused) {
-      // V, W and H are formed
-    } else if (!wide && b == 32) {  // W = C V
-      hipLaunchKernelGGL(k_cv32, dim3(2 * cv_rb), dim3(512), 0, st, C, p, V, W, cv_part, cv_ticket);
-      OCM_CHECK_LAUNCH("k_cv32");
-    } else {
-      rc = dgemm(C, p, V, b, W, b, p, b, p, ksplit, planes, st);
-      if (rc) return rc;
-    }
-    if (it < next_rr) {
-      // W is not needed again (recomputed next iteration).  One CholQR pass
-      // keeps span(W) exactly; the basis that feeds Rayleigh–Ritz (the
-      // iteration before a test) gets the second pass for orthonormality to
-      // rounding.
-      rc = orth(W, V, 500 + it, it == next_rr - 1 ? 2 : 1);
-      if (rc) return rc;
-      continue;
-    }
-    if (fused) {
-      // Rayleigh–Ritz on the unrotated block: H = VᵀW, the projection
-      // residual R = W − V·H and S = RᵀR, Jacobi on H; the test reads
-      // ‖R z_i‖ (at the Jacobi's end).  With θ wanted, R/S, C·R, G2 = Rᵀ(C·R) and the
-      // deflation of the whole block run on side streams beside the Jacobi
-      // (they need no Ritz rotation: k_theta_combine adds its terms later).
-      // (The eigenproblem of H on the host — implicit QL, ocm_hostla.h —
-      // measured slower: ≈ 50–90 µs of QL plus two round trips against the
-      // 135 µs Jacobi, profiles/r05m_eig_timeline.txt.)
-      if (!basis_fused) {
-        hipLaunchKernelGGL(k_atb32, dim3(CQ_G), dim3(256), 0, st, V, W, p, cq_part, cq_ticket, H);
-        OCM_CHECK_LAUNCH("k_atb32 H");
-      }
-      // two side streams when θ is wanted: A deflates the block and runs θ3;
-      // B forms R and S (handed to the Jacobi's test in flight), then C·R and
-      // G2.  The Jacobi stays on the launch stream, queued first: it then
-      // starts at once on an idle chip (107 µs; 128–145 µs when it started
-      // behind the deflation's workgroups with the θ3 chain on the launch
-      // stream, r05s4–r05s7)
-      hipStream_t sa = st, sb = st;
-      rc = eig_side_init(ctx);  // the streams and events (the test's read-back event too)
-      if (rc) return rc;
-      if (theta_mode) {
-        sa = ctx->eig_side[0];
-        sb = ctx->eig_side[1];
-        OCM_HIP(hipEventRecord(ctx->eig_ev[0], st));
-        OCM_HIP(hipStreamWaitEvent(sa, ctx->eig_ev[0], 0));
-        OCM_HIP(hipStreamWaitEvent(sb, ctx->eig_ev[0], 0));
-      }
-      double* R = T1;
-      double* CR = T2;
-      // S reaches the Jacobi's fused test in flight (ctx->eig_flag)
-      const unsigned epoch = ++ctx->eig_epoch;
-      hipLaunchKernelGGL(k_rr_resid32, dim3(CQ_G), dim3(256), 0, sb, V, W, p, H, R, cq_part, cq_ticket, S,
-                         ctx->eig_flag, epoch);
-      OCM_CHECK_LAUNCH("k_rr_resid32");
-      if (theta_mode) {
-        hipLaunchKernelGGL(k_cv32, dim3(2 * cv_rb), dim3(512), 0, sb, C, p, R, CR, cv_part, cv_ticket);
-        OCM_CHECK_LAUNCH("k_cv32 CR");
-        if (theta_mode >= 2) {
-          hipLaunchKernelGGL(k_atb32, dim3(CQ_G), dim3(256), 0, sb, R, CR, p, cq_part, cq_ticket, L);  // G2
-          OCM_CHECK_LAUNCH("k_atb32 G2");
-        }
-        OCM_HIP(hipEventRecord(ctx->eig_ev[3], sb));
-        // after B's test inputs: theta_into queues its Δ terms on B too
-        rc = theta_into(V, W, H, b, sa, sb, ctx->eig_sub, tr3);
-        if (rc) return rc;
-        OCM_HIP(hipEventRecord(ctx->eig_ev[2], sa));
-      }
-      // the Jacobi and the test in one launch (the former k_rr_test32's sums)
-      rc = jacobi(H, b, 40, theta, Z, st, S, ctx->eig_flag, epoch, k, res);
-      if (rc) return rc;
-      OCM_HIP(hipMemcpyAsync(hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
-      OCM_HIP(hipEventRecord(ctx->eig_ev[6], st));
-      // R (= T1) and CR are reused below: side stream B is done with them
-      if (theta_mode) OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[3], 0));
-      // the outputs of a converged test are queued before the host has read
-      // it (the GPU would idle through the round trip otherwise): the Ritz
-      // vectors V·Z into T1, λ and the eigenvectors, then θ once side stream
-      // A is done.  A test that fails leaves them to be overwritten.
-      hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, V, p, Z, T1);  // Ritz vectors
-      OCM_CHECK_LAUNCH("k_cq_apply32 ritz");
-      hipLaunchKernelGGL(k_extract_signfix, dim3(k), dim3(256), 0, st, T1, p, b, k, evecs_out, theta, evals_out, rcond,
-                         inv_out);
-      OCM_CHECK_LAUNCH("k_extract_signfix");
-      if (theta_mode) {  // (the deflation operands and the θ3 arena are reused by the next test too)
-        OCM_HIP(hipStreamWaitEvent(st, ctx->eig_ev[2], 0));
-        hipLaunchKernelGGL(k_theta_combine, dim3(1), dim3(256), 0, st, theta, Z, S, L, tr3, b, k, slice == 0 ? 1 : 0,
-                           theta_mode >= 2 ? 1 : 0, theta_out);
-        OCM_CHECK_LAUNCH("k_theta_combine");
-      }
-      OCM_HIP(hipEventSynchronize(ctx->eig_ev[6]));
-      bool waited_out = false;
-      for (int i = 0; i < k; ++i) waited_out |= hres[b + i] < 0.0;
-      if (waited_out) {
-        // the fused test gave up waiting for S (side stream B not scheduled
-        // within ≈ 1 s): the launch stream has since waited for B's event, so
-        // the same Jacobi + test runs again with S complete (the same Z and λ;
-        // the outputs queued above read them before this rewrites them)
-        ++ctx->eig_test_reruns;
-        rc = jacobi(H, b, 40, theta, Z, st, S, ctx->eig_flag, epoch, k, res, OCM_JACOBI_SPINS_1S);
-        if (rc) return rc;
-        OCM_HIP(hipMemcpyAsync(hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
-        OCM_HIP(hipStreamSynchronize(st));
-        for (int i = 0; i < k; ++i)
-          if (hres[b + i] < 0.0) return ocm::fail(OCM_ERR_HIP, "ocm_eig_topk: the Rayleigh-Ritz test's operand S "
-                                                               "was not ready after its producer finished");
-      }
-      double rmax = 0.0;
-      for (int i = 0; i < k; ++i) rmax = std::max(rmax, hres[b + i]);
-      const double scale = std::fabs(hres[0]);
-      if (!(rmax == rmax)) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: NaN in covariance");
-      const double target = tol * (scale > 0 ? scale : 1.0);
-      converged = rmax <= target;
-      if (converged || it == max_iter) {
-        std::swap(V, T1);
-        extracted = true;
-        break;
-      }
-      const double tk = std::fabs(hres[k - 1]);
-      const double tb = std::fabs(hres[b - 1]), t1 = std::fabs(hres[0]);
-      double rate = tk > 0 ? tb / tk : 1.0;
-      // filtered continuation (above) when θ_b bounds a usable interval
-      const double x1 = tb > 0 ? 2.0 * t1 / tb - 1.0 : 0.0, xk = tb > 0 ? 2.0 * tk / tb - 1.0 : 0.0;
-      int dmax = tb > 0 && x1 > 1.0 && std::isfinite(x1) ? cheb_degree_cap(x1) : 1;
-      // (T_2(x_1) > 1e6: a filter of degree 2 would already pass the condition
-      // budget — the plain iteration stays)
-#ifdef OCM_EIG_NO_CHEB  // make exp A/B: the plain iterations throughout
-      const bool use_cheb = false;
-#else
-      const bool use_cheb = dmax >= 2 && tk > tb * (1.0 + 1e-12);
-#endif
-      if (use_cheb) {
-        // per product: the segments restart the recurrence, so a segment of
-        // degree d gains T_d(x_k) (1.2 at d = 2, x_k = 1.05: 0.913 per product
-        // against θ_b/θ_k = 0.976 for the plain iteration, measured on the nuts
-        // spectrum, profiles/r06h_eig_schedule_nuts.txt)
-        rate = std::pow(std::cosh(dmax * std::acosh(xk)), -1.0 / dmax);
-      }
-      const bool measured_same = !use_cheb || cheb_prev;  // the last interval ran the same iteration
-      if (prev_it > 0 && prev_rmax > 0 && measured_same)
-        rate = std::max(rate, std::pow(rmax / prev_rmax, 1.0 / (it - prev_it)));
-      int ahead = 1;
-      if (rate < 0.999) ahead = (int)std::ceil(std::log(target / rmax) / std::log(std::max(rate, 1e-3)));
-      ahead = std::max(1, std::min(ahead, 64));
-      next_rr = std::min(it + ahead, max_iter);
-#ifdef OCM_EIG_TRACE  // make exp diagnostic: the Rayleigh–Ritz schedule
-      fprintf(stderr, "eig test it %d rmax %.3e target %.3e rate %.4f ahead %d cheb %d dmax %d th1/thb %.3e thk/thb %.6f\n",
-              it, rmax, target, rate, ahead, (int)use_cheb, dmax, t1 / tb, tk / tb);
-#endif
-      prev_it = it;
-      prev_rmax = rmax;
-      cheb_prev = use_cheb;
-      if (use_cheb && next_rr > it + 1) {
-        // the filter starts at the orthonormal basis V, whose C·V = W is in hand
-        cheb = true;
-        cheb_beta = tb;
-        cheb_dmax = dmax;
-        y1_from_w = true;
-        Wc = V;
-        Mc = nullptr;
-        Sprev = nullptr;
-        continue;
-      }
-      cheb = false;
-      // the chain continues from W = C·V (span is all it needs) and its factor
-      OCM_HIP(hipMemcpyAsync(Wa, W, pb * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_cq_gram32<false>, dim3(CQ_G), dim3(256), 0, st, Wa, p, nullptr, nullptr, cq_part, cq_ticket,
-                         1, (uint64_t)(1000 + it), Mf);
-      OCM_CHECK_LAUNCH("k_cq_gram32 chain");
-      Wc = Wa;
-      Wn = Wb;
-      Mc = Mf;
-      mslot = 1;
-      Sprev = nullptr;
-      continue;
-    }
-    rc = ritz();
-    if (rc) return rc;
-    if (!wide && b == QB) {  // Ritz vectors V·Z and C·(Ritz vectors) W·Z on the CholQR product kernel
-      hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, V, p, Z, T1);
-      hipLaunchKernelGGL(k_cq_apply32, dim3(CQ_G), dim3(256), 0, st, W, p, Z, T2);
-      OCM_CHECK_LAUNCH("k_cq_apply32 ritz");
-    } else {
-      rc = dgemm(V, b, Z, b, T1, b, p, b, b, 1, nullptr, st);  // Ritz vectors
-      if (rc) return rc;
-      rc = dgemm(W, b, Z, b, T2, b, p, b, b, 1, nullptr, st);  // C · Ritz vectors
-      if (rc) return rc;
-    }
-    std::swap(V, T1);
-    std::swap(W, T2);
-    hipLaunchKernelGGL(k_ritz_residual, dim3(k), dim3(256), 0, st, W, V, theta, p, b, res);
-    OCM_CHECK_LAUNCH("k_ritz_residual");
-    OCM_HIP(hipMemcpyAsync(hres, theta, 2 * (size_t)b * sizeof(double), hipMemcpyDeviceToHost, st));
-    OCM_HIP(hipStreamSynchronize(st));
-    double rmax = 0.0;
-    for (int i = 0; i < k; ++i) rmax = std::max(rmax, hres[b + i]);  // hres: θ (b) then the residuals
-    const double scale = std::fabs(hres[0]);
-    if (!(rmax == rmax)) return ocm::fail(OCM_ERR_ARG, "ocm_eig_topk: NaN in covariance");
-    const double target = tol * (scale > 0 ? scale : 1.0);
-    if (rmax <= target) {
-      converged = true;
-      break;
-    }
-    if (it == max_iter) break;  // keep V, W, theta consistent for the outputs
-    // predicted iterations to the tolerance (at least one, at most 64 untested)
-    const double tk = std::fabs(hres[k - 1]);
-    double rate = tk > 0 ? std::fabs(hres[b - 1]) / tk : 1.0;
-    if (prev_it > 0 && prev_rmax > 0) rate = std::max(rate, std::pow(rmax / prev_rmax, 1.0 / (it - prev_it)));
-    int ahead = 1;
-    if (rate < 0.999) ahead = (int)std::ceil(std::log(target / rmax) / std::log(std::max(rate, 1e-3)));
-    ahead = std::max(1, std::min(ahead, 64));
-    next_rr = std::min(it + ahead, max_iter);
-    prev_it = it;
-    prev_rmax = rmax;
-    // next basis: orth(C · Ritz vectors)
-    OCM_HIP(hipMemcpyAsync(T1, W, pb * sizeof(double), hipMemcpyDeviceToDevice, st));
-    rc = orth(T1, V, 1000 + it, 2);
-    if (rc) return rc;
-  }
-  if (iters_out) *iters_out = std::min(it, max_iter);
-
-  if (!extracted) {
-    hipLaunchKernelGGL(k_extract_signfix, dim3(k), dim3(256), 0, st, V, p, b, k, evecs_out, theta, evals_out);
-    OCM_CHECK_LAUNCH("k_extract_signfix");
-    if (inv_out) hipLaunchKernelGGL(k_inv_evals, dim3(1), dim3(256), 0, st, evals_out, k, rcond, inv_out);
-  }
-
-  if (theta_mode && !fused) {
-    // H_k = V_kᵀ (C V_k): the projected block of the Ritz vectors; deflate
-    // the leading k of them
-    rc = project(V, W, H);
-    if (rc) return rc;
-    rc = theta_into(V, W, H, k, st, st, ctx, theta_out);
-    if (rc) return rc;
-  }
-  return converged ? OCM_OK : ocm::fail(OCM_ERR_NOCONV, "ocm_eig_topk: max_iter reached before tolerance");
+  s.hres = static_cast<double*>(ocm::host_staging(ctx, s.pl.host_doubles * sizeof(double)));
+  if (!s.hres) return OCM_ERR_NOMEM;
+  return s.pl.fused() ? eig_fused32(s, iters_out) : eig_block(s, iters_out);
 }
+
 
 }  // namespace
 

@@ -1,17 +1,20 @@
 """ocm_eig_topk off the fused b = 32 path, against numpy.linalg.eigh.
 
-eig_topk_impl (csrc/ocm_linalg.hip) picks one of four paths from the width b
-of its subspace block, which ``_block`` restates:
+ocm_eig::make_plan (csrc/ocm_eig_plan.h) picks one of four paths from the
+width b of the subspace block, and eig_topk_impl (csrc/ocm_linalg.hip) hands
+over to that path's driver.  ``_block`` restates the choice independently
+(tests/test_eig_plan.py holds make_plan to it over a grid of (p, k)):
 
-* small (p ≤ 64): one Jacobi on C itself, k_small_finish;
-* fused (b = 32, k ≤ 21): what every other eigensolver test runs;
-* plain device (b = 48 for k = 22..32, b = 64 for k = 33..64): split-K dgemm
-  for C·V, k_colnormalize + k_atb_part / k_sum_planes + k_chol +
-  k_trsm_rows<48/64>, k_jacobi_blk<48/64> on the projection, dgemm Ritz
-  rotations, k_ritz_residual, the stand-alone k_extract_signfix and the
-  deflation of k < b columns for θ;
-* wide (k > 64): host b×b steps; here only the clamped blocks near p
-  (b no multiple of 16, b = p = k).
+* small (p ≤ 64), eig_small: one Jacobi on C itself, k_small_finish;
+* fused (b = 32, k ≤ 21), eig_fused32: what every other eigensolver test
+  runs;
+* plain device (b = 48 for k = 22..32, b = 64 for k = 33..64), eig_block:
+  split-K dgemm for C·V, orth_block (k_colnormalize + k_atb_part /
+  k_sum_planes + k_chol + k_trsm_rows<48/64>), ritz (k_jacobi_blk<48/64> on
+  the projection), dgemm Ritz rotations, k_ritz_residual, the stand-alone
+  k_extract_signfix and theta_deflated on k < b columns for θ;
+* wide (k > 64), eig_block with host b×b steps; here only the clamped blocks
+  near p (b no multiple of 16, b = p = k).
 
 Every reference is eigh of the same fp64 matrix.  Tolerances are those of
 the eigensolver tests in test_gpu_kernels.py (same solver contract,
@@ -33,7 +36,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="n
 
 
 def _block(p, k):
-    """The path eig_topk_impl takes for (p, k): "small", the device block
+    """The path ocm_eig_topk takes for (p, k): "small", the device block
     width 32 (fused) / 48 / 64, or ("wide", b)."""
     if p <= 64:
         return "small"
@@ -71,7 +74,7 @@ MODE_CASES = [(300, 30), (256, 40), (100, 70), (50, 20)]
 
 
 def test_case_lists_hit_the_paths_they_claim():
-    """Tests the test: if the block formula in ocm_linalg.hip changes, the
+    """Tests the test: if the block formula in ocm_eig_plan.h changes, the
     lists above must be revisited (this restatement with them)."""
     assert [_block(p, k) for p, k in BLOCK_CASES] == [48] * 4 + [64] * 5 + [("wide", 96), ("wide", 66), ("wide", 66)]
     assert (66, 66) in BLOCK_CASES and _block(66, 66)[1] % 16 != 0  # b = p = k, no multiple of 16
@@ -250,6 +253,41 @@ def test_eig_theta_modes_and_slices(eng, p, k):
     ev, P, th, _ = _solve(eng, Cd, k, 2, inv_out=inv)
     assert bits(ev) == bits(ev2) and bits(P) == bits(P2) and bits(th) == bits(th2)
     assert bits(inv) == bits(eng.inv_evals(ev))
+
+
+def test_eig_first_product_test_converges(eng):
+    """max_iter = 1 on the fused path: eig_fused32 orthonormalises the start
+    block (k_cq_gram32 twice, k_cq_apply32), forms C·V by k_cv32 and runs the
+    Rayleigh–Ritz step on that first product.  C = 3·I: every orthonormal
+    block is invariant, so that one test converges, whatever the block."""
+    p, k = 128, 6
+    assert _block(p, k) == 32
+    evals, evecs, theta, iters = eng.eig_topk(_dev(3.0 * np.eye(p)), k, 2, max_iter=1, dense_fallback=False)
+    ev, P, th = evals.cpu().numpy(), evecs.cpu().numpy(), theta.cpu().numpy()
+    want_th, floor = (p - k) * np.array([3.0, 9.0, 27.0]), 1e-12 * p * np.array([3.0, 9.0, 27.0])
+    print(f"iters {iters}  evals abs {np.abs(ev - 3).max():.2e}  orth {np.abs(P @ P.T - np.eye(k)).max():.2e}  "
+          f"theta rel {np.abs(th / want_th - 1)}")
+    assert iters == 1
+    np.testing.assert_allclose(ev, 3.0, rtol=1e-10)
+    np.testing.assert_allclose(P @ P.T, np.eye(k), rtol=0, atol=1e-10)
+    for m in range(3):
+        np.testing.assert_allclose(th[m], want_th[m], rtol=1e-8, atol=floor[m], err_msg=f"theta{m + 1}")
+
+
+@pytest.mark.parametrize("p,k", [(128, 6), (128, 24)], ids=["128-6-b32", "128-24-b48"])
+def test_eig_first_product_test_fails_cleanly(eng, p, k):
+    """max_iter = 1 on a matrix with a spectrum: one product of a random block
+    is nowhere near the tolerance, so the call reports OcmNotConverged (fused
+    path and b = 48), and the next ordinary solve in the same process is
+    unaffected by the state it left (tickets, the in-flight flag's epoch)."""
+    from ocm._lib import OcmNotConverged
+
+    C, w, V = _gap_case(p, k)
+    Cd = _dev(C)
+    assert _block(p, k) == (32 if k == 6 else 48)
+    with pytest.raises(OcmNotConverged):
+        eng.eig_topk(Cd, k, 2, max_iter=1, dense_fallback=False)
+    _check_eig(_solve(eng, Cd, k, 2), k, w, V, w[k:], f"p={p} k={k} after max_iter=1")
 
 
 def _spy_eig_topk(monkeypatch):
