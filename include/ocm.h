@@ -600,7 +600,12 @@ int ocm_segsum_f64(ocm_ctx* ctx, const double* X, int64_t ldx, int64_t m, int32_
  * per-channel completion counters — the last of a channel's reduction
  * workgroups forms the statistics, one launch per direction fewer — which
  * every call leaves zero.  Calls sharing one scratch must be stream-ordered.
- * All work is stream-ordered (graph-capturable). */
+ * All work is stream-ordered (graph-capturable).
+ * Accuracy of the statistics: the variance is Σx²/M − mean² with Σx and Σx² held in float32 per
+ * thread (t terms each, t = 32 at N·L = 136000, C = 2; f64 across threads), so under a common
+ * offset its relative error grows as (μ/σ)²·2⁻²⁴·t: at most (t + 2)·2⁻²⁴·(1 + (μ/σ)²), measured
+ * 3.5e-5 at |μ|/σ = 100 and that shape (y is then off by up to 1.2e-4 absolute).  The backward's
+ * sums Σdz and Σdz·x̂ are accumulated in f64 per thread. */
 #define OCM_DTYPE_F32 0
 #define OCM_DTYPE_BF16 1
 /* act: OCM_ACT_ELU fuses the ELU (α = 1) that follows every batch norm of the

@@ -324,7 +324,28 @@ __device__ __forceinline__ float bn_grad(const T* dy, const T* ya, int64_t i) {
   return v > 0.f ? g : g * (v + 1.f);
 }
 
-__device__ __forceinline__ void bn_bwd_tail(float a1, float a2, double* red, double* part, unsigned* ticket,
+// One element's terms of Σdz and Σdz·x̂ as doubles; each thread adds them in f64.  Both sums cancel
+// to far below Σ|dz|, and dx subtracts their means from values as small: with float32 accumulators
+// the means were off by up to 17 float32 ulps of themselves, which showed in the elements of dx with
+// dz ≈ 0 and x̂ ≈ 0 (tests/test_gpu_bn.py: more than 8 float32 ulps of |dz| + |Σdz/M| + |x̂·Σdz·x̂/M|).
+// float operands: dz = dy·(1 + min(y, 0)) and x̂ formed in f64 too, so the sums carry no float32
+// rounding at all (2.5 % on the two launches at (512, 3, 2048)).
+__device__ __forceinline__ void bn_bwd_terms(const float*, bool elu, float g, float y, float x, float mu, float is,
+                                             double& dz, double& xh) {
+  const double gd = (double)g;
+  dz = elu ? fma(gd, (double)(y > 0.f ? 0.f : y), gd) : gd;  // (a NaN in y stays one)
+  xh = ((double)x - (double)mu) * (double)is;
+}
+// bf16 operands: the float32 dz and x̂ of the elementwise pass, widened.  Their roundings are random
+// and leave the means within a float32 ulp or so; the bf16 reductions are bound by their
+// instructions, and f64 terms cost 18 % on the two launches at (512, 3, 2048) where this costs 0-3 %
+__device__ __forceinline__ void bn_bwd_terms(const bf16_t*, bool elu, float g, float y, float x, float mu, float is,
+                                             double& dz, double& xh) {
+  dz = (double)(elu ? (y > 0.f ? g : g * (y + 1.f)) : g);
+  xh = (double)((x - mu) * is);
+}
+
+__device__ __forceinline__ void bn_bwd_tail(double a1, double a2, double* red, double* part, unsigned* ticket,
                                             double* sums, float* dgamma, float* dbeta);
 
 // grid (split, C): partial Σdz, Σdz·x̂; the channel's last workgroup forms
@@ -340,7 +361,7 @@ __global__ __launch_bounds__(BN_T) void k_bn_bwd_stats(const T* __restrict__ x, 
   const int c = blockIdx.y, sp = blockIdx.x, split = gridDim.x;
   const float mu = mean[c], is = invstd[c];
   const int total = N * L, step = split * BN_T;
-  float a1 = 0.f, a2 = 0.f;
+  double a1 = 0.0, a2 = 0.0;
   for (int e0 = sp * BN_T + threadIdx.x; e0 < total; e0 += BN_U * step) {
     float g[BN_U], xv[BN_U], yv[BN_U];
 #pragma unroll
@@ -351,10 +372,10 @@ __global__ __launch_bounds__(BN_T) void k_bn_bwd_stats(const T* __restrict__ x, 
     }
 #pragma unroll
     for (int r = 0; r < BN_U; ++r) {
-      if (ELU) g[r] = yv[r] > 0.f ? g[r] : g[r] * (yv[r] + 1.f);
-      a1 += g[r];
-      // padded elements: g = 0, so the (0 − μ)·invstd term adds nothing
-      a2 = fmaf(g[r], (xv[r] - mu) * is, a2);
+      double gz, xh;
+      bn_bwd_terms(dy, ELU, g[r], ELU ? yv[r] : 0.f, xv[r], mu, is, gz, xh);
+      a1 += gz;
+      a2 = fma(gz, xh, a2);  // padded elements: g = 0, so the (0 − μ)·invstd term adds nothing
     }
   }
   bn_bwd_tail(a1, a2, red, part, ticket, sums, dgamma, dbeta);
@@ -374,7 +395,7 @@ __global__ __launch_bounds__(BN_T) void k_bn_bwd_stats8(const T* __restrict__ x,
   const float mu = mean[c], is = invstd[c];
   const int L8 = L / 8, total = N * L8, step = split * BN_T;
   constexpr int U = BN_U8 / 2;  // three tensors: two groups of each in flight
-  float a1 = 0.f, a2 = 0.f;
+  double a1 = 0.0, a2 = 0.0;
   for (int e0 = sp * BN_T + threadIdx.x; e0 < total; e0 += U * step) {
     float g[U][8], xv[U][8], yv[ELU ? U : 1][8];
 #pragma unroll
@@ -387,17 +408,16 @@ __global__ __launch_bounds__(BN_T) void k_bn_bwd_stats8(const T* __restrict__ x,
     for (int r = 0; r < U; ++r)
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float gz = g[r][k];
-        if (ELU) gz = yv[ELU ? r : 0][k] > 0.f ? gz : gz * (yv[ELU ? r : 0][k] + 1.f);
+        double gz, xh;
+        bn_bwd_terms(dy, ELU, g[r][k], ELU ? yv[ELU ? r : 0][k] : 0.f, xv[r][k], mu, is, gz, xh);
         a1 += gz;
-        // padded groups: g = 0, so the (0 − μ)·invstd term adds nothing
-        a2 = fmaf(gz, (xv[r][k] - mu) * is, a2);
+        a2 = fma(gz, xh, a2);  // padded groups: g = 0, so the (0 − μ)·invstd term adds nothing
       }
   }
   bn_bwd_tail(a1, a2, red, part, ticket, sums, dgamma, dbeta);
 }
 
-__device__ __forceinline__ void bn_bwd_tail(float a1, float a2, double* red, double* part, unsigned* ticket,
+__device__ __forceinline__ void bn_bwd_tail(double a1, double a2, double* red, double* part, unsigned* ticket,
                                             double* sums, float* dgamma, float* dbeta) {
   const int c = blockIdx.y, sp = blockIdx.x, split = gridDim.x;
   const double s1 = block_sum_f64(a1, red);

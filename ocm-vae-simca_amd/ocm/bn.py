@@ -116,6 +116,9 @@ class FastBatchNorm1d(nn.BatchNorm1d):
             # eval (running statistics), host tensors, cumulative-average momentum: the stock module
             y = super().forward(x)
             return F.elu(y) if self.act == ACT_ELU else y
+        if x.shape[0] * x.shape[2] == 1:
+            # as nn.BatchNorm1d in training mode (the kernels would return β: var = 0)
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
         # the batch count is incremented by the statistics kernel (one launch fewer)
         nbt = (self.num_batches_tracked if self.track_running_stats and self.num_batches_tracked is not None
                and self.num_batches_tracked.dtype == torch.int64 and self.num_batches_tracked.is_cuda else None)
